@@ -74,3 +74,28 @@ def grad_digest(grads, stride=997):
         out[k + '|sum'] = g.sum().reshape(1)
         out[k + '|sample'] = g[::stride].clone()
     return out
+
+
+# rpe_index: the oracle against the compiled reference operator (tests/test_rpe_index_cpu.py), (B, H, Lq, Lk, nb, dtype)
+RPE_INDEX_REF_CASES = [(2, 3, 197, 197, 50, torch.float32), (1, 2, 50, 37, 9, torch.float64), (3, 1, 5, 577, 50, torch.float16)]
+
+
+def rpe_index_ref_inputs():
+    """[(nb, x, index, g)] of RPE_INDEX_REF_CASES from the global generator seeded 1, in the order the check draws them
+    (no output gradient g for float16: the reference's half backward has no defined order)."""
+    torch.manual_seed(1)
+    out = []
+    for (B, H, Lq, Lk, nb, dt) in RPE_INDEX_REF_CASES:
+        x = torch.randn(B, H, Lq, nb).to(dt)
+        index = torch.randint(0, nb, (Lq, Lk), dtype=torch.int32)
+        g = torch.randn(B, H, Lq, Lk).to(dt) if dt != torch.float16 else None
+        out.append((nb, x, index, g))
+    return out
+
+
+def digest(a):
+    """sha256 of an array's bytes (torch tensor or numpy array, C order)."""
+    import hashlib
+    import numpy as np
+    a = a.detach().contiguous().numpy() if torch.is_tensor(a) else a
+    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()

@@ -628,6 +628,29 @@ def irpe_zoo():
     print('irpe_zoo.json', {k: v['n_params'] for k, v in meta.items()})
 
 
+def rpe_index_ref():
+    """Digests of what the reference's own compiled operator (oracle/build_ref.py -> oracle/_ref) returns on the inputs of
+    tests/test_rpe_index_cpu.py::test_oracle_matches_compiled_reference: forward_cpu and, single-threaded, backward_cpu."""
+    from fixture_utils import RPE_INDEX_REF_CASES, digest, rpe_index_ref_inputs
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(HERE)), 'oracle'))
+    import build_ref
+    build_ref.build()
+    ref = build_ref.load_ref()
+    threads = torch.get_num_threads()
+    torch.set_num_threads(1)           # the reference's accumulation order is only defined single-threaded
+    cases = []
+    for case, (nb, x, index, g) in zip(RPE_INDEX_REF_CASES, rpe_index_ref_inputs()):
+        rec = dict(case=list(case[:5]) + [str(case[5])], x=digest(x), index=digest(index), y=digest(ref.forward_cpu(x, index)))
+        if g is not None:
+            gin = torch.zeros(x.shape, dtype=x.dtype)
+            ref.backward_cpu(gin, g, index)
+            rec.update(g=digest(g), gin=digest(gin))
+        cases.append(rec)
+    torch.set_num_threads(threads)
+    json.dump(dict(cases=cases), open(os.path.join(HERE, 'rpe_index_ref.json'), 'w'), indent=1)
+    print('rpe_index_ref.json', len(cases), 'cases')
+
+
 if __name__ == '__main__':
     assert refshim.have_reference(), "needs the reference checkout at /root/reference"
     which = sys.argv[1:] or ['autoformer', 'irpe']
@@ -655,3 +678,5 @@ if __name__ == '__main__':
         tinyclip_ckpt()
     if 'irpe_zoo' in which:
         irpe_zoo()
+    if 'rpe_index_ref' in which:
+        rpe_index_ref()

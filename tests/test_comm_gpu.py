@@ -132,7 +132,7 @@ def test_bench_n4_code_path_rehearsed_over_gloo(tmp_path):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), WORLD_SIZE=str(world), LOCAL_RANK="0",
                CREAM_DIST_BACKEND="gloo", CREAM_BENCH_EXTRA=str(tmp_path / "extra.json"))
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "2", "--warmup", "1", "--batch", "8",
-           "--no-cpu-baseline", "--no-host-leg"]
+           "--full", "--no-cpu-baseline", "--no-host-leg"]
     procs = []
     for r in range(world):
         e = dict(env, RANK=str(r))

@@ -9,9 +9,12 @@ import pytest
 import torch
 
 from conftest import ROOT
+from helpers import load_json
 from oracle import rpe_index_oracle as O
 
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
+sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+from fixture_utils import RPE_INDEX_REF_CASES, digest, rpe_index_ref_inputs  # noqa: E402
 
 
 def _flat_gather(x, index):
@@ -40,27 +43,35 @@ def test_oracle_matches_reference_selftest_shapes():
 
 
 def test_oracle_matches_compiled_reference():
+    """The oracle against the reference's own compiled operator (oracle/_ref): bit for bit what it returns, live where
+    oracle/_ref is built and always against the digests recorded from it (tests/golden/rpe_index_ref.json,
+    `make_golden.py rpe_index_ref`) on the same seeded inputs."""
     from build_ref import load_ref
     ref = load_ref()
-    if ref is None:
-        pytest.skip("oracle/_ref not built (needs /root/reference once)")
-    torch.manual_seed(1)
-    for (B, H, Lq, Lk, nb, dt) in [(2, 3, 197, 197, 50, torch.float32), (1, 2, 50, 37, 9, torch.float64),
-                                   (3, 1, 5, 577, 50, torch.float16)]:
-        x = torch.randn(B, H, Lq, nb).to(dt)
-        index = torch.randint(0, nb, (Lq, Lk), dtype=torch.int32)
-        y_ref = ref.forward_cpu(x, index)
-        y = O.fwd(x.view(torch.int16).numpy() if dt == torch.float16 else x.numpy(), index.numpy())
-        want = y_ref.view(torch.int16).numpy() if dt == torch.float16 else y_ref.numpy()
-        np.testing.assert_array_equal(y.view(want.dtype), want)
-        if dt != torch.float16:
-            torch.set_num_threads(1)   # the reference's order is only defined single-threaded
-            g = torch.randn(B, H, Lq, Lk).to(dt)
-            gin_ref = torch.zeros(B, H, Lq, nb, dtype=dt)
-            ref.backward_cpu(gin_ref, g, index)
+    cases = load_json("rpe_index_ref.json")["cases"]
+    inputs = rpe_index_ref_inputs()
+    assert len(cases) == len(inputs) == len(RPE_INDEX_REF_CASES)
+    for (nb, x, index, g), rec in zip(inputs, cases):
+        # the digests hold for these inputs only: the seeded draws must be the ones they were recorded on
+        assert (digest(x), digest(index)) == (rec["x"], rec["index"]), rec["case"]
+        half = x.dtype == torch.float16
+        y = O.fwd(x.view(torch.int16).numpy() if half else x.numpy(), index.numpy())
+        assert digest(y) == rec["y"], rec["case"]
+        if ref is not None:
+            y_ref = ref.forward_cpu(x, index)
+            want = y_ref.view(torch.int16).numpy() if half else y_ref.numpy()
+            np.testing.assert_array_equal(y.view(want.dtype), want)
+        if g is not None:
+            assert digest(g) == rec["g"], rec["case"]
             gin = O.bwd(g.numpy(), index.numpy(), nb)
-            np.testing.assert_array_equal(gin, gin_ref.numpy())
-            torch.set_num_threads(torch.get_num_threads())
+            assert digest(gin) == rec["gin"], rec["case"]
+            if ref is not None:
+                threads = torch.get_num_threads()
+                torch.set_num_threads(1)   # the reference's order is only defined single-threaded
+                gin_ref = torch.zeros(x.shape, dtype=x.dtype)
+                ref.backward_cpu(gin_ref, g, index)
+                torch.set_num_threads(threads)
+                np.testing.assert_array_equal(gin, gin_ref.numpy())
 
 
 @pytest.mark.parametrize("dt", [torch.float32, torch.float64, torch.float16, torch.bfloat16])

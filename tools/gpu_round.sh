@@ -13,7 +13,7 @@ echo "pytest exit $?"; tail -3 $OUT/${TAG}_pytest_gpu.log
 fi
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/${TAG}_smoke.log 2>&1
 echo "smoke exit $?"; tail -2 $OUT/${TAG}_smoke.log
-CREAM_BENCH_EXTRA=$OUT/${TAG}_bench_extra.json timeout 600 python bench.py --steps $STEPS --warmup 10 > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
+CREAM_BENCH_EXTRA=$OUT/${TAG}_bench_extra.json timeout 600 python bench.py --full --steps $STEPS --warmup 10 > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
 echo "bench exit $?"; cat $OUT/${TAG}_bench.json
 cd /tmp
 CREAM_BENCH_EXTRA=/dev/null timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_prof -o step -- python $REPO/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-kernel-timing --no-host-leg > $OUT/${TAG}_prof_bench.json 2> $OUT/${TAG}_prof.err
@@ -42,7 +42,7 @@ done
 cd $REPO
 # the other measured configurations: config 2 (supernet-T, fixed subnet), config 4 (rpe_index
 # micro-benchmark + one RPEAttention layer), sub-network evaluation, host-side profile of the step
-CREAM_BENCH_EXTRA=$OUT/${TAG}_bench_config2_extra.json timeout 300 python bench.py --supernet T --subnet T --steps 40 --warmup 10 --no-cpu-baseline > $OUT/${TAG}_bench_config2.json 2> $OUT/${TAG}_bench_config2.err
+CREAM_BENCH_EXTRA=$OUT/${TAG}_bench_config2_extra.json timeout 300 python bench.py --full --supernet T --subnet T --steps 40 --warmup 10 --no-cpu-baseline > $OUT/${TAG}_bench_config2.json 2> $OUT/${TAG}_bench_config2.err
 echo "config2 exit $?"; cat $OUT/${TAG}_bench_config2.json | cut -c1-400
 timeout 300 python tools/bench_rpe_index.py > $OUT/${TAG}_rpe_index_microbench.jsonl 2> $OUT/${TAG}_rpe_index_microbench.err
 echo "rpe microbench exit $?"; cut -c1-300 $OUT/${TAG}_rpe_index_microbench.jsonl
