@@ -129,6 +129,10 @@ SIGNATURES = {
     "cream_block_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cream_block_bwd_workspace": (_i64, [_vp, _vp, _vp, _vp]),
     "cream_block_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _vp, _vp, _i, _vp, _vp]),
+    "cream_image_augment_workspace": (_i64, [_i, _i, _i, _i]),
+    "cream_image_augment_u8": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _i64, _vp]),
+    "cream_image_batch_plan_aug": (_i64, [_vp, _i, _i, _i, _vp, _i]),
+    "cream_image_batch_transform_aug": (_i, [_vp, _vp, _i64, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i64, _vp]),
 }
 
 MAX_GRAD_JOBS = 24
@@ -148,6 +152,11 @@ class ImageDesc(ctypes.Structure):
                 [("tmp_off", _i64)] +
                 [(n, _c.c_int32) for n in ("erase_top", "erase_left", "erase_h", "erase_w")] +
                 [("erase_seed", _c.c_uint32), ("reserved", _c.c_int32)])
+
+
+class AugOp(ctypes.Structure):
+    """struct cream_aug_op of include/cream_amd.h (64 bytes)."""
+    _fields_ = [("kind", _c.c_int32), ("arg", _c.c_int32), ("factor", _f), ("fill", _c.c_uint32), ("m", _c.c_double * 6)]
 
 
 class SliceJob(ctypes.Structure):

@@ -232,25 +232,188 @@ def erase_noise_reference(seed, C, H, W):
     return (np.sqrt(np.float32(-2) * np.log(u1)) * np.cos(np.float32(6.28318530717958647692) * u2)).astype(np.float32)
 
 
+# ---- RandAugment of the training recipe (`--aa rand-m9-mstd0.5-inc1`: supernet_train.py:111, lib/datasets.py:189-202) ----------
+# timm 0.3.2's rand_augment_transform with the hparams transforms_imagenet_train builds (img_mean fill, BICUBIC, translate_pct
+# 0.45).  timm is third-party and not vendored in the reference: the policy grammar and the draws are restated from its published
+# definition (parity unpinned, as train_crop_params); the OPERATIONS are Pillow's and are pinned against Pillow.  Each op of an image
+# becomes one descriptor (AugDesc) that csrc/image_augment.hip applies on the device.
+AUG_NONE, AUG_AUTOCONTRAST, AUG_EQUALIZE, AUG_INVERT, AUG_POSTERIZE, AUG_SOLARIZE, AUG_SOLARIZE_ADD = 0, 1, 2, 3, 4, 5, 6
+AUG_COLOR, AUG_CONTRAST, AUG_BRIGHTNESS, AUG_SHARPNESS, AUG_AFFINE = 7, 8, 9, 10, 11       # CREAM_AUG_* of include/cream_amd.h
+AUG_IDENTITY = (1.0, 0.0, 0.0, 0.0, 1.0, 0.0)
+
+# timm's _RAND_INCREASING_TRANSFORMS, in its order (the indices np.random.choice draws)
+RAND_INCREASING_TRANSFORMS = ('AutoContrast', 'Equalize', 'Invert', 'Rotate', 'PosterizeIncreasing', 'SolarizeIncreasing',
+                              'SolarizeAdd', 'ColorIncreasing', 'ContrastIncreasing', 'BrightnessIncreasing',
+                              'SharpnessIncreasing', 'ShearX', 'ShearY', 'TranslateXRel', 'TranslateYRel')
+_MAX_LEVEL = 10.
+
+
+class AugDesc(tuple):
+    """One op of one image: (kind, arg, factor, fill, m) — struct cream_aug_op of include/cream_amd.h.  arg: posterize bits /
+    solarize threshold / solarize-add addend; factor: the blend factor of the four enhance ops (the device gets it as float32, as
+    Pillow's blend does); fill: the affine op's (R, G, B); m: the affine op's 6 doubles (input point of an output pixel centre)."""
+    __slots__ = ()
+
+    def __new__(cls, kind, arg=0, factor=1.0, fill=(0, 0, 0), m=AUG_IDENTITY):
+        return tuple.__new__(cls, (int(kind), int(arg), float(factor), tuple(int(v) for v in fill), tuple(float(v) for v in m)))
+
+    kind = property(lambda s: s[0])
+    arg = property(lambda s: s[1])
+    factor = property(lambda s: s[2])
+    fill = property(lambda s: s[3])
+    m = property(lambda s: s[4])
+
+
+class RandAugmentPolicy(tuple):
+    """Parsed `rand-m{M}[-n{N}][-mstd{S}]-inc1`: (magnitude, num_layers, magnitude_std, fill)."""
+    __slots__ = ()
+    magnitude = property(lambda s: s[0])
+    num_layers = property(lambda s: s[1])
+    magnitude_std = property(lambda s: s[2])
+    fill = property(lambda s: s[3])
+
+
+def parse_rand_augment(policy, mean=IMAGENET_DEFAULT_MEAN, interpolation='bicubic'):
+    """timm 0.3.2's rand_augment_transform(config_str, hparams) grammar for the policies this device path covers.  `m` is required,
+    `n` (2), `mstd` (0) optional, `inc1` required (the op list _RAND_INCREASING_TRANSFORMS); anything else — `inc0`, `-w`
+    weights, an unknown section, an interpolation other than bicubic — raises ValueError (that recipe stays on the host path).
+    fill = transforms_imagenet_train's img_mean: tuple(min(255, round(255 * m)) for m in mean)."""
+    import re
+    if interpolation != 'bicubic':
+        raise ValueError(f"RandAugment on the device: interpolation {interpolation!r} (only 'bicubic')")
+    if not isinstance(policy, str):
+        raise ValueError(f"RandAugment policy must be a string, got {policy!r}")
+    parts = policy.split('-')
+    if parts[0] != 'rand':
+        raise ValueError(f"not a RandAugment policy: {policy!r}")
+    magnitude, num_layers, mstd, inc = None, 2, 0.0, False
+    for c in parts[1:]:
+        cs = re.split(r'(\d.*)', c)
+        if len(cs) < 2:
+            raise ValueError(f"RandAugment policy {policy!r}: section {c!r} has no value")
+        key, val = cs[:2]
+        if key == 'm':
+            magnitude = int(val)
+        elif key == 'n':
+            num_layers = int(val)
+        elif key == 'mstd':
+            mstd = float(val)
+        elif key == 'inc' and val == '1':
+            inc = True
+        else:                                           # inc0 (timm 0.3.2 reads it as inc1: bool('0')), -w weights, ...
+            raise ValueError(f"RandAugment policy {policy!r}: section {c!r} is not on the device path")
+    if magnitude is None or not inc:
+        raise ValueError(f"RandAugment policy {policy!r}: 'm' and 'inc1' are required")
+    if num_layers < 0 or not math.isfinite(mstd) or mstd < 0:
+        raise ValueError(f"RandAugment policy {policy!r}: bad n / mstd")
+    fill = tuple(min(255, round(255 * m)) for m in mean)
+    return RandAugmentPolicy((magnitude, num_layers, mstd, fill))
+
+
+def _rotate_matrix(degrees, width, height):
+    """Image.rotate(degrees, BICUBIC) of a (width, height) image as the affine matrix it hands to Image.transform (Pillow's
+    Image.py: angle % 360, matrix entries rounded to 15 digits, centre (w / 2, h / 2))."""
+    angle = degrees % 360.0
+    if angle == 0:
+        return AUG_IDENTITY
+    center = (width / 2, height / 2)
+    angle = -math.radians(angle)
+    m = [round(math.cos(angle), 15), round(math.sin(angle), 15), 0.0, round(-math.sin(angle), 15), round(math.cos(angle), 15), 0.0]
+    a, b, c, d, e, f = m
+    x, y = -center[0], -center[1]
+    m[2], m[5] = a * x + b * y + c, d * x + e * y + f
+    m[2] += center[0]
+    m[5] += center[1]
+    return tuple(m)
+
+
+def rand_augment_params(rng, np_rng, policy, height, width):
+    """The draws of timm's RandAugment.__call__ / AugmentOp.__call__ for ONE (height, width) image, in their order of calls:
+    the op indices from `np_rng` (a numpy RandomState: np.random.choice(ops, N) with replacement), then per chosen op the gate
+    (rng.random() > 0.5 skips it), the magnitude (rng.gauss(M, S) when S > 0, clipped to [0, 10]) and the level function's sign
+    draw (rng.random() > 0.5 negates).  `rng` is a random.Random; `policy` a string or parse_rand_augment's result.
+    -> list of N AugDesc (a skipped op is AUG_NONE)."""
+    if not isinstance(policy, RandAugmentPolicy):
+        policy = parse_rand_augment(policy)
+    M, N, S, fill = policy
+    out = []
+    for idx in np_rng.choice(len(RAND_INCREASING_TRANSFORMS), N):
+        name = RAND_INCREASING_TRANSFORMS[int(idx)]
+        if rng.random() > 0.5:
+            out.append(AugDesc(AUG_NONE))
+            continue
+        magnitude = M
+        if S > 0:
+            magnitude = rng.gauss(magnitude, S)
+        magnitude = min(_MAX_LEVEL, max(0, magnitude))
+        negate = lambda v: -v if rng.random() > 0.5 else v                                       # noqa: E731
+        if name == 'AutoContrast':
+            out.append(AugDesc(AUG_AUTOCONTRAST))
+        elif name == 'Equalize':
+            out.append(AugDesc(AUG_EQUALIZE))
+        elif name == 'Invert':
+            out.append(AugDesc(AUG_INVERT))
+        elif name == 'Rotate':
+            out.append(AugDesc(AUG_AFFINE, fill=fill, m=_rotate_matrix(negate((magnitude / _MAX_LEVEL) * 30.), width, height)))
+        elif name == 'PosterizeIncreasing':
+            out.append(AugDesc(AUG_POSTERIZE, arg=4 - int((magnitude / _MAX_LEVEL) * 4)))
+        elif name == 'SolarizeIncreasing':
+            out.append(AugDesc(AUG_SOLARIZE, arg=256 - int((magnitude / _MAX_LEVEL) * 256)))
+        elif name == 'SolarizeAdd':
+            out.append(AugDesc(AUG_SOLARIZE_ADD, arg=int((magnitude / _MAX_LEVEL) * 110)))
+        elif name.endswith('Increasing'):                                 # Color / Contrast / Brightness / Sharpness
+            kind = {'Color': AUG_COLOR, 'Contrast': AUG_CONTRAST, 'Brightness': AUG_BRIGHTNESS,
+                    'Sharpness': AUG_SHARPNESS}[name[:-len('Increasing')]]
+            out.append(AugDesc(kind, factor=1.0 + negate((magnitude / _MAX_LEVEL) * .9)))
+        elif name in ('ShearX', 'ShearY'):
+            s = negate((magnitude / _MAX_LEVEL) * 0.3)
+            out.append(AugDesc(AUG_AFFINE, fill=fill, m=(1, s, 0, 0, 1, 0) if name == 'ShearX' else (1, 0, 0, s, 1, 0)))
+        else:                                                             # TranslateXRel / TranslateYRel
+            pct = negate((magnitude / _MAX_LEVEL) * 0.45)
+            out.append(AugDesc(AUG_AFFINE, fill=fill, m=(1, 0, pct * width, 0, 1, 0) if name == 'TranslateXRel'
+                               else (1, 0, 0, 0, 1, pct * height)))
+    return out
+
+
+def aug_op_array(aug_ops):
+    """Per-image lists of AugDesc (all of one length N) -> (ctypes array of B * N struct cream_aug_op, N)."""
+    from .. import _lib
+    n = len(aug_ops[0]) if aug_ops else 0
+    if any(len(a) != n for a in aug_ops):
+        raise ValueError("every image needs the same number of augmentation descriptors")
+    arr = (_lib.AugOp * max(1, len(aug_ops) * n))()
+    for i, ops in enumerate(aug_ops):
+        for k, op in enumerate(ops):
+            d = arr[i * n + k]
+            d.kind, d.arg, d.factor = op[0], op[1], op[2]
+            d.fill = op[3][0] | (op[3][1] << 8) | (op[3][2] << 16)
+            for j in range(6):
+                d.m[j] = op[4][j]
+    return arr, n
+
+
 class DeviceTransform:
     """A batch of decoded frames (HWC uint8 RGB arrays of any sizes) -> (B, 3, S, S) float32 on the device, as the reference's
     per-image transforms produce it: F.crop -> Pillow's bicubic F.resize -> window (CenterCrop) -> mirror -> ToTensor -> Normalize,
     three launches for the whole batch (cream_image_batch_transform; byte-exact with Pillow's resize, bit-exact float ops).
-    The frames travel as ONE packed uint8 buffer (each frame at a 4-byte aligned offset) from pinned memory; RandAugment /
-    RandomErasing of the training recipe stay host-side (out of scope)."""
+    With `aug_ops` (per image, rand_augment_params) RandAugment runs between the mirror and ToTensor, on the uint8 image Pillow
+    would hold there (cream_image_batch_transform_aug).  The frames travel as ONE packed uint8 buffer (each frame at a 4-byte
+    aligned offset) from pinned memory."""
 
     def __init__(self, input_size=224, mean=IMAGENET_DEFAULT_MEAN, std=IMAGENET_DEFAULT_STD, device="cuda"):
         import ctypes
         self.size, self.device = int(input_size), torch.device(device)
+        self.mean = tuple(mean)
         self._mean = (ctypes.c_float * 3)(*mean)
         self._std = (ctypes.c_float * 3)(*std)
         self._ws = None
         self._pool = None                      # packing threads (numpy's large copies release the GIL)
         self.pack_threads = 8
 
-    def plan(self, shapes, params):
+    def plan(self, shapes, params, aug=None):
         """shapes: [(H, W)], params: [(box, resized, window[, flip[, erase]])] with erase = None | (top, left, h, w, seed)
-        (random_erasing_params) -> (ImageDesc array (planned), packed byte count, workspace bytes)."""
+        (random_erasing_params); aug: None or aug_op_array's (ops, ops_per_image)
+        -> (ImageDesc array (planned), packed byte count, workspace bytes)."""
         from .. import _lib
         B = len(shapes)
         descs = (_lib.ImageDesc * B)()
@@ -265,19 +428,24 @@ class DeviceTransform:
             if len(p) > 4 and p[4] is not None:
                 d.erase_top, d.erase_left, d.erase_h, d.erase_w, d.erase_seed = p[4]
             off += (h * w * 3 + 3) // 4 * 4
-        ws = _lib.load().cream_image_batch_plan(descs, B, self.size, self.size)
+        if aug is None:
+            ws = _lib.load().cream_image_batch_plan(descs, B, self.size, self.size)
+        else:
+            ws = _lib.load().cream_image_batch_plan_aug(descs, B, self.size, self.size, aug[0], aug[1])
         if ws < 0:
-            _lib.check(int(ws), "cream_image_batch_plan")
+            _lib.check(int(ws), "cream_image_batch_plan" if aug is None else "cream_image_batch_plan_aug")
         return descs, off, int(ws)
 
-    def __call__(self, frames, params):
-        """frames: list of (H, W, 3) uint8 numpy arrays / tensors; params as for `plan`."""
+    def __call__(self, frames, params, aug_ops=None):
+        """frames: list of (H, W, 3) uint8 numpy arrays / tensors; params as for `plan`; aug_ops: None, or per image the list of
+        RandAugment descriptors (AugDesc, rand_augment_params; the same count for every image) applied after the mirror."""
         import ctypes
         import numpy as np
         from .. import _lib
         B = len(frames)
         shapes = [tuple(f.shape[:2]) for f in frames]
-        descs, nbytes, ws_bytes = self.plan(shapes, params)
+        aug = aug_op_array(aug_ops) if aug_ops is not None else None
+        descs, nbytes, ws_bytes = self.plan(shapes, params, aug)
         packed = torch.empty(nbytes, dtype=torch.uint8, pin_memory=self.device.type == "cuda")
         pk = packed.numpy()
 
@@ -304,10 +472,19 @@ class DeviceTransform:
                 self._ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=self.device)
             out = torch.empty((B, 3, self.size, self.size), dtype=torch.float32, device=self.device)
             st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-            _lib.check(_lib.load().cream_image_batch_transform(
-                ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(pix.data_ptr()), nbytes, descs, ctypes.c_void_p(dd.data_ptr()), B,
-                self.size, self.size, self._mean, self._std, ctypes.c_void_p(self._ws.data_ptr()), self._ws.numel(), st),
-                "cream_image_batch_transform")
+            if aug is None:
+                _lib.check(_lib.load().cream_image_batch_transform(
+                    ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(pix.data_ptr()), nbytes, descs, ctypes.c_void_p(dd.data_ptr()),
+                    B, self.size, self.size, self._mean, self._std, ctypes.c_void_p(self._ws.data_ptr()), self._ws.numel(), st),
+                    "cream_image_batch_transform")
+            else:
+                raw_ops = torch.frombuffer(bytearray(bytes(aug[0])), dtype=torch.uint8)
+                od = (raw_ops.pin_memory() if self.device.type == "cuda" else raw_ops).to(self.device, non_blocking=True)
+                _lib.check(_lib.load().cream_image_batch_transform_aug(
+                    ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(pix.data_ptr()), nbytes, descs, ctypes.c_void_p(dd.data_ptr()),
+                    B, self.size, self.size, self._mean, self._std, aug[0], ctypes.c_void_p(od.data_ptr()), aug[1],
+                    ctypes.c_void_p(self._ws.data_ptr()), self._ws.numel(), st), "cream_image_batch_transform_aug")
+                od.record_stream(torch.cuda.current_stream())
             # the staging tensors are read by the copies / kernels enqueued above
             pix.record_stream(torch.cuda.current_stream())
             dd.record_stream(torch.cuda.current_stream())
@@ -319,14 +496,23 @@ class DeviceBatches:
     (frames: list of (H, W, 3) uint8 arrays, labels: int sequence) and yields (samples (B, 3, S, S) fp32 on the device, labels int64
     on the device) — what `DataLoader(ImageFolder(root, transform=build_transform(...)))` yields in the reference (lib/datasets.py:
     222-239, supernet_train.py:222-241), with the transform moved behind the loader and onto the device.
-    mode 'eval': Resize + CenterCrop; mode 'train': RandomResizedCrop + flip (+ RandomErasing with `reprob` > 0) from `rng`."""
+    mode 'eval': Resize + CenterCrop; mode 'train': RandomResizedCrop + flip (+ RandAugment with `auto_augment`, e.g.
+    'rand-m9-mstd0.5-inc1', op choices from `np_rng`) (+ RandomErasing with `reprob` > 0) from `rng`, in timm's order of draws
+    per image.  An `auto_augment` policy outside the device path raises ValueError (parse_rand_augment)."""
 
-    def __init__(self, loader, transform, mode="eval", rng=None, reprob=0.0):
+    def __init__(self, loader, transform, mode="eval", rng=None, reprob=0.0, auto_augment=None, np_rng=None):
         import random as _random
         if mode not in ("eval", "train"):
             raise ValueError(f"unknown mode {mode!r}")
         self.loader, self.transform, self.mode, self.reprob = loader, transform, mode, float(reprob)
         self.rng = rng if rng is not None else _random.Random(0)
+        self.auto_augment = None
+        if auto_augment is not None:
+            import numpy as np
+            if mode != "train":
+                raise ValueError("auto_augment belongs to the training transform (mode='train')")
+            self.auto_augment = parse_rand_augment(auto_augment, getattr(transform, "mean", IMAGENET_DEFAULT_MEAN))
+            self.np_rng = np_rng if np_rng is not None else np.random.RandomState(0)
 
     def params_for(self, shapes):
         size = self.transform.size
@@ -335,14 +521,19 @@ class DeviceBatches:
         out = []
         for h, w in shapes:
             box, resized, window, flip = train_crop_params(h, w, self.rng, size)
+            ops = rand_augment_params(self.rng, self.np_rng, self.auto_augment, size, size) if self.auto_augment else None
             erase = random_erasing_params(self.rng, size, size, self.reprob) if self.reprob > 0 else None
-            out.append((box, resized, window, flip, erase))
+            out.append((box, resized, window, flip, erase) + ((ops,) if self.auto_augment else ()))
         return out
 
     def __iter__(self):
         for frames, labels in self.loader:
             shapes = [tuple(f.shape[:2]) for f in frames]
-            samples = self.transform(frames, self.params_for(shapes))
+            params = self.params_for(shapes)
+            if self.auto_augment is not None:            # (box, resized, window, flip, erase, RandAugment ops)
+                samples = self.transform(frames, [p[:5] for p in params], aug_ops=[p[5] for p in params])
+            else:
+                samples = self.transform(frames, params)
             yield samples, torch.as_tensor(labels, dtype=torch.int64).to(samples.device, non_blocking=True)
 
 

@@ -3,8 +3,8 @@
 // Reference: AutoFormer/lib/datasets.py:189-220 (`build_transform`):
 //     eval :  Resize(int(256 / 224 * input_size), interpolation=3) -> CenterCrop(input_size) -> ToTensor -> Normalize
 //     train:  timm create_transform(is_training=True, interpolation='bicubic') = RandomResizedCropAndInterpolation ->
-//             RandomHorizontalFlip -> [RandAugment, host side, out of scope] -> ToTensor -> Normalize -> RandomErasing ('pixel' mode:
-//             box from the host, standard-normal noise from a counter-based hash in the vertical-pass kernel)
+//             RandomHorizontalFlip -> [RandAugment: image_augment.hip] -> ToTensor -> Normalize -> RandomErasing ('pixel' mode:
+//             box from the host, standard-normal noise from a counter-based hash in the float tail)
 // On the PIL images of the reference's ImageFolder every resize above is Pillow's `Image.resize(size, BICUBIC)` (third-party, not
 // vendored in /root/reference).  These kernels restate Pillow's 8-bit algorithm (libImaging/Resample.c: precompute_coeffs,
 // normalize_coeffs_8bpc, ImagingResampleHorizontal_8bpc, ImagingResampleVertical_8bpc; bicubic a = -0.5; 22 fixed-point bits) integer
@@ -22,15 +22,18 @@
 //   V  vertical pass + ToTensor + Normalize (+ mirror): a thread owns 4 consecutive output columns x 3 channels of one output row —
 //      three aligned 4-byte loads per tap — and writes three 16-byte vectors of the (B, 3, out_h, out_w) fp32 batch.
 // Traffic per image of a 500 x 375 frame -> 224 x 224: 0.56 MB read, 0.25 MB intermediate written + read, 0.6 MB written.
+// With RandAugment (cream_image_batch_transform_aug) the vertical pass writes the mirrored uint8 image instead (one RGBX word per
+// pixel), the op layers of image_augment.hip follow, and the last of them ends in the same float tail (store_normalized4).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <type_traits>
 
 #include "cream_amd.h"
+#include "image_common.hpp"
 
 namespace {
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using cream_image::store_normalized4;
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int PRECISION_BITS = 32 - 8 - 2;
@@ -91,23 +94,6 @@ template <bool WIDE> __device__ __forceinline__ int madk(int acc, int v, int k) 
     else return acc + __mul24(v, k);
 }
 __device__ __forceinline__ bool needs_wide(int k) { return k >= (1 << 23) || k <= -(1 << 23); }
-
-// standard-normal noise of RandomErasing's 'pixel' mode: two 32-bit counter-based hashes of (seed, channel, row, column) through
-// Box-Muller (autoformer/data.py: erase_noise_reference restates it)
-__device__ __forceinline__ uint32_t mix32(uint32_t x) {
-    x ^= x >> 16; x *= 0x7feb352du;
-    x ^= x >> 15; x *= 0x846ca68bu;
-    x ^= x >> 16;
-    return x;
-}
-__device__ __forceinline__ float erase_noise(uint32_t seed, int c, int y, int x) {
-    const uint32_t key = mix32(seed ^ ((uint32_t)(c + 1) * 0x9E3779B9u));
-    const uint32_t h1 = mix32(key ^ (((uint32_t)y << 16) | (uint32_t)x));
-    const uint32_t h2 = mix32(h1 ^ 0x85EBCA6Bu);
-    const float u1 = ((float)(h1 >> 8) + 1.0f) * (1.0f / 16777216.0f);          // (0, 1]
-    const float u2 = (float)(h2 >> 8) * (1.0f / 16777216.0f);                   // [0, 1)
-    return sqrtf(-2.0f * logf(u1)) * cosf(6.28318530717958647692f * u2);
-}
 
 __device__ __forceinline__ int clip8(int v) {
     v >>= PRECISION_BITS;
@@ -285,10 +271,13 @@ __global__ __launch_bounds__(256) void image_resample_h_kernel(uint8_t* __restri
 }
 
 // ---- V + ToTensor + Normalize ----------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void image_resample_v_kernel(float* __restrict__ out, const uint8_t* __restrict__ tmp,
-                                                               const Dev* __restrict__ descs, const int* __restrict__ tabs, int out_h,
-                                                               int out_w, int V_ROWS, int ksx, int ksy, float m0, float m1, float m2,
-                                                               float s0, float s1, float s2)
+// U8OUT: the mirrored uint8 image instead, one RGBX word per pixel (R | G << 8 | B << 16) at out_rgbx + (b, yo, xo), for the
+// RandAugment layers (image_augment.hip) that follow it
+template <bool U8OUT>
+__global__ __launch_bounds__(256) void image_resample_v_kernel(float* __restrict__ out, uint32_t* __restrict__ out_rgbx,
+                                                               const uint8_t* __restrict__ tmp, const Dev* __restrict__ descs,
+                                                               const int* __restrict__ tabs, int out_h, int out_w, int V_ROWS, int ksx,
+                                                               int ksy, float m0, float m1, float m2, float s0, float s1, float s2)
 {
     const Dev d = descs[blockIdx.y];
     const TabLayout L(ksx, ksy, out_h, out_w);
@@ -323,24 +312,20 @@ __global__ __launch_bounds__(256) void image_resample_v_kernel(float* __restrict
     };
     if (wide) col_pass(std::true_type{});
     else col_pass(std::false_type{});
-    // torchvision F.to_tensor: float(v) / 255; F.normalize: (x - mean) / std — two IEEE float32 divisions, no contraction
-    const float mean[3] = {m0, m1, m2}, sd[3] = {s0, s1, s2};
-    float* ob = out + (int64_t)blockIdx.y * 3 * out_h * out_w + (int64_t)yo * out_w;
+    int u8[12];
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        f32x4 v;
+    for (int e = 0; e < 12; ++e) u8[e] = clip8(acc[e]);
+    const int xo = d.flip ? out_w - 4 - 4 * gx : 4 * gx;
+    if constexpr (U8OUT) {
+        u32x4 q;
 #pragma unroll
-        for (int px = 0; px < 4; ++px) {
-            const float x = (float)clip8(acc[3 * px + c]) / 255.f;
-            v[d.flip ? 3 - px : px] = (x - mean[c]) / sd[c];
-        }
-        const int xo = d.flip ? out_w - 4 - 4 * gx : 4 * gx;
-        if (d.erase_h > 0 && yo >= d.erase_top && yo < d.erase_top + d.erase_h) {      // RandomErasing, mode 'pixel'
-#pragma unroll
-            for (int px = 0; px < 4; ++px)
-                if (xo + px >= d.erase_left && xo + px < d.erase_left + d.erase_w) v[px] = erase_noise(d.erase_seed, c, yo, xo + px);
-        }
-        *reinterpret_cast<f32x4*>(ob + (int64_t)c * out_h * out_w + xo) = v;
+        for (int px = 0; px < 4; ++px)
+            q[d.flip ? 3 - px : px] = (uint32_t)u8[3 * px] | ((uint32_t)u8[3 * px + 1] << 8) | ((uint32_t)u8[3 * px + 2] << 16);
+        *reinterpret_cast<u32x4*>(out_rgbx + ((int64_t)blockIdx.y * out_h + yo) * out_w + xo) = q;
+    } else {
+        const float mean[3] = {m0, m1, m2}, sd[3] = {s0, s1, s2};
+        store_normalized4(out + (int64_t)blockIdx.y * 3 * out_h * out_w + (int64_t)yo * out_w, (int64_t)out_h * out_w, xo, yo,
+                          d.flip != 0, u8, mean, sd, d);
     }
 }
 
@@ -461,7 +446,74 @@ extern "C" int cream_image_batch_transform(float* out, const uint8_t* pixels, in
     if (rc != CREAM_OK) return rc;
     // 3. vertical pass + ToTensor + Normalize (+ mirror, RandomErasing)
     const int vr = v_rows(out_w);
-    hipLaunchKernelGGL(image_resample_v_kernel, dim3((out_h + vr - 1) / vr, B), dim3(256), 0, st, out, tmp, descs_dev, tabs, out_h, out_w,
-                       vr, bt.ksx, bt.ksy, mean[0], mean[1], mean[2], stdev[0], stdev[1], stdev[2]);
+    hipLaunchKernelGGL(image_resample_v_kernel<false>, dim3((out_h + vr - 1) / vr, B), dim3(256), 0, st, out, nullptr, tmp, descs_dev, tabs,
+                       out_h, out_w, vr, bt.ksx, bt.ksy, mean[0], mean[1], mean[2], stdev[0], stdev[1], stdev[2]);
     return hipGetLastError() == hipSuccess ? CREAM_OK : CREAM_ERR_LAUNCH;
+}
+
+// ---- with RandAugment: the uint8 image of the crop / resize / mirror, the op layers (image_augment.hip), the float tail ------------
+namespace {
+constexpr int AUG_MAX_H = 4096;                                     // keeps the whole-image sums of the op layers in int32
+int64_t aug_image_bytes(int B, int out_h, int out_w) { return align16((int64_t)B * out_h * out_w * 4); }
+int aug_buffers(int ops_per_image) { return ops_per_image >= 2 ? 2 : 1; }
+}  // namespace
+
+extern "C" int64_t cream_image_batch_plan_aug(cream_image_desc* descs, int B, int out_h, int out_w, const cream_aug_op* ops,
+                                              int ops_per_image)
+{
+    if (ops_per_image < 0 || ops_per_image > CREAM_AUG_MAX_OPS || (ops_per_image > 0 && !ops)) return CREAM_ERR_BAD_ARG;
+    const int64_t plain = cream_image_batch_plan(descs, B, out_h, out_w);
+    if (plain < 0 || ops_per_image == 0) return plain;
+    if (out_h > AUG_MAX_H) return CREAM_ERR_TOO_LARGE;
+    const int rc = cream_image::check_aug_ops(ops, (int64_t)B * ops_per_image);
+    if (rc != CREAM_OK) return rc;
+    return plain + aug_buffers(ops_per_image) * aug_image_bytes(B, out_h, out_w);       // [tables | rows | image | image]
+}
+
+extern "C" int cream_image_batch_transform_aug(float* out, const uint8_t* pixels, int64_t pixels_bytes, const cream_image_desc* descs,
+                                               const cream_image_desc* descs_dev, int B, int out_h, int out_w, const float* mean,
+                                               const float* stdev, const cream_aug_op* ops, const cream_aug_op* ops_dev,
+                                               int ops_per_image, void* workspace, int64_t workspace_bytes, void* stream)
+{
+    if (ops_per_image == 0)
+        return cream_image_batch_transform(out, pixels, pixels_bytes, descs, descs_dev, B, out_h, out_w, mean, stdev, workspace,
+                                           workspace_bytes, stream);
+    if (B == 0) return CREAM_OK;
+    if (!out || !pixels || !descs || !descs_dev || !mean || !stdev || !workspace || !ops || !ops_dev || !shape_ok(B, out_h, out_w) ||
+        ops_per_image < 0 || ops_per_image > CREAM_AUG_MAX_OPS)
+        return CREAM_ERR_BAD_ARG;
+    if (((uintptr_t)out) % 16 || ((uintptr_t)pixels) % 4 || ((uintptr_t)workspace) % 16 || ((uintptr_t)descs_dev) % 8 ||
+        ((uintptr_t)ops_dev) % 8 || pixels_bytes % 4)
+        return CREAM_ERR_BAD_ARG;
+    if (out_h > AUG_MAX_H) return CREAM_ERR_TOO_LARGE;
+    Batch bt;
+    int rc = survey(nullptr, descs, B, out_h, out_w, pixels_bytes, bt);
+    if (rc != CREAM_OK) return rc;
+    rc = cream_image::check_aug_ops(ops, (int64_t)B * ops_per_image);
+    if (rc != CREAM_OK) return rc;
+    const int64_t img_bytes = aug_image_bytes(B, out_h, out_w);
+    if (workspace_bytes < bt.tab_bytes + bt.tmp_bytes + aug_buffers(ops_per_image) * img_bytes) return CREAM_ERR_BAD_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    int* tabs = reinterpret_cast<int*>(workspace);
+    uint8_t* tmp = reinterpret_cast<uint8_t*>(workspace) + bt.tab_bytes;
+    uint32_t* img = reinterpret_cast<uint32_t*>(tmp + bt.tmp_bytes);
+    uint32_t* img2 = ops_per_image >= 2 ? reinterpret_cast<uint32_t*>(tmp + bt.tmp_bytes + img_bytes) : nullptr;
+    // 1. + 2. the coefficient tables and the horizontal pass of cream_image_batch_transform
+    hipLaunchKernelGGL(image_coeff_kernel, dim3(2, B), dim3(256), 0, st, tabs, descs_dev, out_h, out_w, bt.ksx, bt.ksy);
+    if (hipGetLastError() != hipSuccess) return CREAM_ERR_LAUNCH;
+    if (h_lds_bytes(bt.ksx, bt.box_w, out_w, 8) <= 40 * 1024)
+        rc = launch_h<8>(tmp, pixels, descs_dev, tabs, B, out_h, out_w, bt.max_rows, bt.ksx, bt.ksy, bt.box_w, st);
+    else if (h_lds_bytes(bt.ksx, bt.box_w, out_w, 4) <= LDS_H_BYTES)
+        rc = launch_h<4>(tmp, pixels, descs_dev, tabs, B, out_h, out_w, bt.max_rows, bt.ksx, bt.ksy, bt.box_w, st);
+    else if (h_lds_bytes(bt.ksx, bt.box_w, out_w, 2) <= LDS_H_BYTES)
+        rc = launch_h<2>(tmp, pixels, descs_dev, tabs, B, out_h, out_w, bt.max_rows, bt.ksx, bt.ksy, bt.box_w, st);
+    else rc = launch_h<1>(tmp, pixels, descs_dev, tabs, B, out_h, out_w, bt.max_rows, bt.ksx, bt.ksy, bt.box_w, st);
+    if (rc != CREAM_OK) return rc;
+    // 3. vertical pass -> the mirrored uint8 image
+    const int vr = v_rows(out_w);
+    hipLaunchKernelGGL(image_resample_v_kernel<true>, dim3((out_h + vr - 1) / vr, B), dim3(256), 0, st, nullptr, img, tmp, descs_dev, tabs,
+                       out_h, out_w, vr, bt.ksx, bt.ksy, 0.f, 0.f, 0.f, 1.f, 1.f, 1.f);
+    if (hipGetLastError() != hipSuccess) return CREAM_ERR_LAUNCH;
+    // 4. one launch per op layer, the last one ending in ToTensor -> Normalize -> RandomErasing
+    return cream_image::launch_aug_tail(out, img, img2, ops_dev, ops_per_image, B, out_h, out_w, descs_dev, mean, stdev, st);
 }

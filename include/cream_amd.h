@@ -737,6 +737,65 @@ int cream_block_prof_kinds(void);
 const char* cream_block_prof_name(int kind);
 int cream_block_prof_collect(double* total_ms, int64_t* launches, double* flops, double* bytes);
 
+/* ---- RandAugment of the training recipe on the device (csrc/image_augment.hip) -----------------
+ * `--aa rand-m9-mstd0.5-inc1` (AutoFormer/supernet_train.py:111; timm 0.3.2's RandAugment inside create_transform, between the
+ * flip and ToTensor: lib/datasets.py:189-202).  The host draws the ops of every image (cream_amd/autoformer/data.py:
+ * rand_augment_params); each op is one descriptor, Pillow's operation on the uint8 RGB image restated integer for integer (the
+ * affine op in doubles, in libImaging's order of IEEE operations):
+ *   NONE          identity (an op skipped by its gate)
+ *   AUTOCONTRAST  ImageOps.autocontrast(cutoff 0)          EQUALIZE   ImageOps.equalize       INVERT  255 - x
+ *   POSTERIZE     x & ~(2^(8 - arg) - 1), arg = bits 0..8  SOLARIZE   x < arg ? x : 255 - x, arg = threshold 0..256
+ *   SOLARIZE_ADD  x < 128 ? min(255, x + arg) : x, arg 0..255
+ *   COLOR / CONTRAST / BRIGHTNESS / SHARPNESS   ImageEnhance: Image.blend(degenerate, image, factor) in float32; degenerate = grey
+ *                 level (19595 R + 38470 G + 7471 B + 0x8000) >> 16 / its mean over the image / 0 / ImageFilter.SMOOTH
+ *   AFFINE        Image.transform(size, AFFINE, m, BICUBIC, fillcolor): output pixel (x, y) samples the input at
+ *                 (m0 (x + .5) + m1 (y + .5) + m2, m3 (x + .5) + m4 (y + .5) + m5); outside the image: `fill` (R | G << 8 | B << 16).
+ *                 Rotate / ShearX / ShearY / TranslateXRel / TranslateYRel are this op (Image.rotate's own matrix, from the host).
+ * Per image ops_per_image descriptors, applied in order: ops[b * ops_per_image + k].  Every entry point validates the host copy
+ * (unknown kind, arg out of range, non-finite factor or matrix: CREAM_ERR_BAD_ARG) before anything is enqueued; the kernels read
+ * the device copy (ops_dev), which must hold the same bytes. */
+#define CREAM_AUG_NONE          0
+#define CREAM_AUG_AUTOCONTRAST  1
+#define CREAM_AUG_EQUALIZE      2
+#define CREAM_AUG_INVERT        3
+#define CREAM_AUG_POSTERIZE     4
+#define CREAM_AUG_SOLARIZE      5
+#define CREAM_AUG_SOLARIZE_ADD  6
+#define CREAM_AUG_COLOR         7
+#define CREAM_AUG_CONTRAST      8
+#define CREAM_AUG_BRIGHTNESS    9
+#define CREAM_AUG_SHARPNESS    10
+#define CREAM_AUG_AFFINE       11
+#define CREAM_AUG_MAX_OPS      16  /* ops_per_image */
+typedef struct cream_aug_op {
+    int32_t kind;                                   /* CREAM_AUG_* */
+    int32_t arg;                                    /* posterize bits / solarize threshold / solarize-add addend */
+    float factor;                                   /* blend factor of the four enhance ops */
+    uint32_t fill;                                  /* affine: R | G << 8 | B << 16 */
+    double m[6];                                    /* affine matrix */
+} cream_aug_op;
+#ifdef __cplusplus
+static_assert(sizeof(cream_aug_op) == 64, "cream_aug_op is 64 bytes");
+#else
+_Static_assert(sizeof(cream_aug_op) == 64, "cream_aug_op is 64 bytes");
+#endif
+/* B HWC uint8 RGB images of one size H x W (1 <= W <= 1024) -> the augmented images, dst and src packed (B, H, W, 3), not
+ * overlapping; one launch per op layer.  workspace: cream_image_augment_workspace(B, H, W, ops_per_image) bytes, 16-byte aligned
+ * (NULL when that is 0).  ops_per_image 0 copies nothing and returns CREAM_OK. */
+int64_t cream_image_augment_workspace(int B, int H, int W, int ops_per_image);
+int cream_image_augment_u8(uint8_t* dst, const uint8_t* src, int B, int H, int W, const cream_aug_op* ops, const cream_aug_op* ops_dev,
+                           int ops_per_image, void* workspace, int64_t workspace_bytes, void* stream);
+/* The training transform with RandAugment: crop -> bicubic resize -> mirror (the uint8 image Pillow holds there: the coefficient
+ * and horizontal-pass kernels of cream_image_batch_transform, then its vertical pass writing uint8) -> the op layers -> ToTensor ->
+ * Normalize -> RandomErasing (the float tail of cream_image_batch_transform, fused into the last layer).  Same conventions as
+ * cream_image_batch_plan / cream_image_batch_transform; _plan_aug also validates the ops and returns a workspace size >= the plain
+ * plan's.  ops_per_image == 0 is cream_image_batch_transform. */
+int64_t cream_image_batch_plan_aug(cream_image_desc* descs, int B, int out_h, int out_w, const cream_aug_op* ops, int ops_per_image);
+int cream_image_batch_transform_aug(float* out, const uint8_t* pixels, int64_t pixels_bytes, const cream_image_desc* descs,
+                                    const cream_image_desc* descs_dev, int B, int out_h, int out_w, const float* mean,
+                                    const float* stdev, const cream_aug_op* ops, const cream_aug_op* ops_dev, int ops_per_image,
+                                    void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }  /* extern "C" */
 #endif

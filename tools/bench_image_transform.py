@@ -1,7 +1,10 @@
 """The device input transform (cream_image_batch_transform) on a batch of 128 ImageNet-shaped frames: kernel time of the two launches
 (HIP events on the launch stream, frames already resident in HBM), the end-to-end call with the host packing and the PCIe copy, and
 Pillow + torch on the host cores beside it (the reference's per-image path, one thread).
-    python tools/bench_image_transform.py [eval|train]   ->  one JSON line"""
+    python tools/bench_image_transform.py [eval|train|train-aa]   ->  one JSON line
+train-aa: the training transform with RandAugment ('rand-m9-mstd0.5-inc1', cream_image_batch_transform_aug): kernel time per batch
+with and without the augmentation launches (the same crops, mirrors and erasing boxes), and Pillow's own RandAugment per image
+on one core (timm's ops on the 224 x 224 crop)."""
 import ctypes
 import json
 import random
@@ -17,8 +20,101 @@ from cream_amd import _lib                                   # noqa: E402
 from cream_amd.autoformer import data as D                   # noqa: E402
 
 
+def _timed(call, st, reps=20):
+    for _ in range(3):
+        assert call() == 0
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    ev[0].record(st)
+    for _ in range(reps):
+        call()
+    ev[1].record(st)
+    torch.cuda.synchronize()
+    return ev[0].elapsed_time(ev[1]) / reps
+
+
+def pillow_rand_augment(im, ops):
+    """timm's op calls for the AugDesc chain of one image (the host path the device replaces)."""
+    from PIL import Image, ImageEnhance, ImageOps
+    for kind, arg, factor, fill, m in ops:
+        if kind == D.AUG_AUTOCONTRAST:
+            im = ImageOps.autocontrast(im)
+        elif kind == D.AUG_EQUALIZE:
+            im = ImageOps.equalize(im)
+        elif kind == D.AUG_INVERT:
+            im = ImageOps.invert(im)
+        elif kind == D.AUG_POSTERIZE:
+            im = ImageOps.posterize(im, arg)
+        elif kind == D.AUG_SOLARIZE:
+            im = ImageOps.solarize(im, arg)
+        elif kind == D.AUG_SOLARIZE_ADD:
+            im = im.point([min(255, i + arg) if i < 128 else i for i in range(256)] * 3)
+        elif kind in (D.AUG_COLOR, D.AUG_CONTRAST, D.AUG_BRIGHTNESS, D.AUG_SHARPNESS):
+            im = {D.AUG_COLOR: ImageEnhance.Color, D.AUG_CONTRAST: ImageEnhance.Contrast, D.AUG_BRIGHTNESS: ImageEnhance.Brightness,
+                  D.AUG_SHARPNESS: ImageEnhance.Sharpness}[kind](im).enhance(factor)
+        elif kind == D.AUG_AFFINE:
+            im = im.transform(im.size, Image.AFFINE, m, Image.BICUBIC, fillcolor=fill)
+    return im
+
+
+def main_train_aa():
+    B, size, dev = 128, 224, "cuda:0"
+    rng = np.random.default_rng(0)
+    pr, nr = random.Random(0), np.random.RandomState(0)
+    mix = [(375, 500), (500, 375), (333, 500)]                   # ImageNet's three most common frame sizes
+    shapes = [mix[i % len(mix)] for i in range(B)]
+    frames = [rng.integers(0, 256, (h, w, 3), dtype=np.uint8) for h, w in shapes]
+    policy = D.parse_rand_augment("rand-m9-mstd0.5-inc1")
+    params, chains = [], []
+    for h, w in shapes:                                          # timm's order of draws per image
+        crop = D.train_crop_params(h, w, pr)
+        chains.append(D.rand_augment_params(pr, nr, policy, size, size))
+        params.append(crop + (D.random_erasing_params(pr, size, size, 0.25),))
+    T = D.DeviceTransform(size, device=dev)
+    arr, n = D.aug_op_array(chains)
+    descs, nbytes, ws = T.plan(shapes, params, (arr, n))
+    pix = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    for d, f in zip(descs, frames):
+        pix[d.offset:d.offset + f.size] = torch.from_numpy(f.reshape(-1)).to(dev)
+    dd = torch.frombuffer(bytearray(bytes(descs)), dtype=torch.uint8).to(dev)
+    od = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
+    wsb = torch.empty(ws, dtype=torch.uint8, device=dev)
+    out = torch.empty(B, 3, size, size, device=dev)
+    p = lambda t: ctypes.c_void_p(t.data_ptr())
+    lib = _lib.load()
+    st = torch.cuda.current_stream()
+    s = ctypes.c_void_p(st.cuda_stream)
+    plain = lambda: lib.cream_image_batch_transform(p(out), p(pix), nbytes, descs, p(dd), B, size, size, T._mean, T._std, p(wsb), ws, s)
+    aug = lambda: lib.cream_image_batch_transform_aug(p(out), p(pix), nbytes, descs, p(dd), B, size, size, T._mean, T._std, arr, p(od),
+                                                      n, p(wsb), ws, s)
+    ms_plain, ms_aug = [], []
+    for _ in range(3):                                           # alternated, median of three windows each
+        ms_plain.append(_timed(plain, st))
+        ms_aug.append(_timed(aug, st))
+    ms_plain, ms_aug = sorted(ms_plain)[1], sorted(ms_aug)[1]
+    applied = sum(op.kind != D.AUG_NONE for c in chains for op in c)
+    cpu = None
+    try:
+        from PIL import Image
+        crops = [np.ascontiguousarray(rng.integers(0, 256, (size, size, 3), dtype=np.uint8)) for _ in range(64)]
+        t0 = time.perf_counter()
+        for c, ops in zip(crops, chains):
+            pillow_rand_augment(Image.fromarray(c), ops)
+        cpu = (time.perf_counter() - t0) / len(crops)
+    except ImportError:
+        pass
+    print(json.dumps({"workload": f"input transform (train, RandAugment rand-m9-mstd0.5-inc1, reprob 0.25): {B} decoded frames "
+                                  f"(333x500 .. 500x375) -> ({B}, 3, {size}, {size}) fp32",
+                      "kernels_ms_plain": round(ms_plain, 4), "kernels_ms_with_rand_augment": round(ms_aug, 4),
+                      "rand_augment_us_per_128_frames": round((ms_aug - ms_plain) * 1e3, 1), "estimate_us_per_128_frames": 50,
+                      "ops_per_image": n, "ops_applied_in_batch": applied,
+                      "images_per_sec_kernels_with_rand_augment": round(B / ms_aug * 1e3),
+                      "cpu_pillow_rand_augment_ms_per_image_1_core": None if cpu is None else round(cpu * 1e3, 3)}))
+
+
 def main():
     pipeline = sys.argv[1] if len(sys.argv) > 1 else "train"
+    if pipeline == "train-aa":
+        return main_train_aa()
     B, size, dev = 128, 224, "cuda:0"
     rng = np.random.default_rng(0)
     pr = random.Random(0)
