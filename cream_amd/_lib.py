@@ -50,6 +50,10 @@ SIGNATURES = {
     "cream_irpe_attn_fwd": (_i, [_vp, _vp]),
     "cream_irpe_attn_bwd": (_i, [_vp, _vp]),
     "cream_irpe_table_grad": (_i, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _i, _i, _i, _f, _vp]),
+    "cream_irpe_attn2_check": (_i, [_vp, _i]),
+    "cream_irpe_attn2_fwd": (_i, [_vp, _vp]),
+    "cream_irpe_attn2_bwd": (_i, [_vp, _vp]),
+    "cream_irpe_table_grad2": (_i, [_vp, _vp, _i64, _i64, _i64, _i, _vp, _i64, _i64, _i64, _i, _i, _i, _i, _f, _vp]),
     "cream_attn_rpe2d_padded_len": (_i, [_i]),
     "cream_attn_rpe2d_dtab_parts": (_i, [_i, _i]),
     "cream_attn_rpe2d_bwd_mode": (_i, [_i]),
@@ -186,6 +190,12 @@ class IrpeAttnDesc(ctypes.Structure):
                 [(n, _vp) for n in ("dout", "dq", "dk", "dv")] + [(n, _i64) for n in ("dsb", "dsn", "dsh")] +
                 [(n, _vp) for n in ("delta", "lkg", "gg", "dlk", "dlq", "bq", "bk")] + [(n, _i64) for n in ("bq_hs", "bk_hs")] +
                 [("causal", _c.c_int32), ("reserved", _c.c_int32), ("dropout_p", _c.c_float), ("dropout_seed", _c.c_uint32)])
+
+
+class IrpeAttn2Desc(ctypes.Structure):
+    """struct cream_irpe_attn2_desc of include/cream_amd.h."""
+    _fields_ = ([("base", IrpeAttnDesc), ("head_dim", _c.c_int32), ("row_width", _c.c_int32), ("key_pad", _vp)] +
+                [(n, _i64) for n in ("key_pad_sb", "osb", "osn", "dosb", "dosn")])
 
 
 class ParamJob(ctypes.Structure):

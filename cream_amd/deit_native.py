@@ -55,7 +55,7 @@ def _block_supported(blk, L, dev):
     if not (isinstance(blk.drop_path, nn.Identity) or hasattr(blk.drop_path, "drop_prob")):     # DropPath: per-sample factors in the node
         return False
     rpes = (at.rpe_q, at.rpe_k, at.rpe_v)
-    if any(r is not None and type(r) is not iRPE for r in rpes):
+    if any(r is not None and (type(r) is not iRPE or r.num_buckets > 64) for r in rpes):    # the node runs the 64-column kernels
         return False
     p = float(at.attn_drop.p) if tr else 0.0
     return at.qkv.weight.dtype == torch.float32 and irpe_fused.usable(torch.bfloat16, dev, 64, L, rpes, dropout_p=p)

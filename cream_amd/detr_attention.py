@@ -11,7 +11,16 @@ Sequence-first tensors (L, N, E) like `nn.MultiheadAttention`, packed `in_proj_w
     A[attn_mask] / A[:, :, :, key_padding_mask] = -inf ;  P = dropout(softmax(A)) ;  out = P v + rpe_v(P) ;  out_proj
 and, with `need_weights`, the head-averaged P is returned as well (:383-387).
 
-DETR's heads are 32 wide (256 / 8): the fused iRPE attention kernels (head_dim 64) do not apply, the map is formed.
+Two paths.  The FUSED path (cream_amd.irpe_fused.attention_qkv on csrc/irpe_attn_x.hip: 32-wide heads, up to 128 buckets
+on k, the key padding mask and attention dropout inside the kernels, nothing of size L^2 in HBM) is taken when it
+can be: device tensors under bf16 autocast (or bf16 inputs), `need_weights=False`, no `attn_mask`, self-attention shapes
+(key / value as long as query) with L = S = h * w <= 2048, and `irpe_fused.usable(...)` true for the module's rpe
+configuration — e.g. the published recipe `--enc_rpe2d rpe-2.0-product-ctx-1-k` (81 buckets on k).  q, k, v go to the
+kernels as strided views of the projections and the result comes back sequence-first: no permute copies.  Everything
+else — fp32, `need_weights=True`, an `attn_mask`, the CPU, `CREAM_IRPE_FUSED=0` — takes the COMPOSED path below, which
+forms the (N, heads, L, S) map exactly as before.  The reference's encoder layer calls `self_attn(q, k, value=src, ...)[0]`
+and drops the weights while leaving `need_weights` at its default True: a caller who drops them passes
+`need_weights=False` to reach the fused kernels (the default of the argument is the reference's and does not change).
 What `nn.MultiheadAttention` offers beyond DETR's use (`add_bias_kv`, `add_zero_attn`, `kdim` / `vdim`, static k / v)
 is refused at construction instead of being silently approximated.
 """
@@ -19,6 +28,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import irpe_fused
 from .irpe import build_rpe
 
 
@@ -57,6 +67,20 @@ class RPEMultiheadAttention(nn.Module):
 
         return part(query, 0), part(key, 1), part(value, 2)
 
+    def _fused_ok(self, q, L, S, N, need_weights, attn_mask, hw):
+        """The fused kernels apply: bf16 projections on a device (bf16 autocast or bf16 inputs), no weights wanted, no
+        attn_mask, self-attention shapes on an h x w map, and a configuration the kernels implement."""
+        if need_weights or attn_mask is not None or L != S or not q.is_cuda or q.dtype != torch.bfloat16:
+            return False
+        has_rpe = self.rpe_k is not None or self.rpe_q is not None or self.rpe_v is not None
+        if has_rpe and (hw is None or L != hw[0] * hw[1]):
+            return False                                     # (the composed path raises its assertion)
+        if (N * self.embed_dim) % 8 or self.embed_dim % 8:
+            return False
+        return irpe_fused.usable(q.dtype, q.device, self.head_dim, L, (self.rpe_q, self.rpe_k, self.rpe_v),
+                                 dropout_p=self.dropout if self.training else 0.0, key_padding=True,
+                                 hw=hw if has_rpe else None)
+
     def forward(self, query, key, value, key_padding_mask=None, need_weights=True, attn_mask=None, hw=None):
         """query (L, N, E), key / value (S, N, E); key_padding_mask (N, S) bool / byte; attn_mask (L, S) or
         (N * heads, L, S), bool or additive float; hw = (height, width) of the feature map when an rpe is present."""
@@ -65,6 +89,14 @@ class RPEMultiheadAttention(nn.Module):
         H, hd = self.num_heads, self.head_dim
         assert E == self.embed_dim and key.shape[:2] == value.shape[:2]
         q, k, v = self._project(query, key, value)
+        if self._fused_ok(q, L, S, N, need_weights, attn_mask, hw):
+            # (scale q) . k + rpe_k(scale q) + rpe_q(scale k)^T, mask, softmax, dropout, P v + rpe_v(P) in one launch
+            # (two backward); (L, N, E) projections as (N, L, H, hd) views, the result sequence-first for out_proj
+            view = lambda t: t.view(L, N, H, hd).permute(1, 0, 2, 3)                      # noqa: E731
+            out = irpe_fused.attention_qkv(view(q), view(k), view(v), float(hd) ** -0.5, self.rpe_q, self.rpe_k, self.rpe_v,
+                                           key_padding_mask=key_padding_mask,
+                                           dropout_p=self.dropout if self.training else 0.0, hw=hw, seq_first=True)
+            return self.out_proj(out), None
         q = q * float(hd) ** -0.5                                                       # :235
         q = q.reshape(L, N, H, hd).permute(1, 2, 0, 3)                                    # (N, H, L, hd)
         k = k.reshape(S, N, H, hd).permute(1, 2, 0, 3)

@@ -308,6 +308,59 @@ int cream_irpe_attn_bwd(const cream_irpe_attn_desc* d, void* stream);
 int cream_irpe_table_grad(float* out, const void* x, int64_t xsb, int64_t xsn, int64_t xsh, const void* y, int64_t ysb,
                           int64_t ysn, int64_t ysh, int B, int H, int L, float mul, void* stream);
 
+/* ---- fused iRPE attention, generalised: 32- or 64-wide heads, up to 128 buckets, key padding mask -------------
+ * The same operator as cream_irpe_attn_fwd / _bwd (same formulas, launches and conventions; csrc/irpe_attn_x.hip),
+ * for the callers those entry points refuse: DETR-with-iRPE's encoder self-attention (d_model 256 / 8 heads = 32,
+ * `--enc_rpe2d rpe-2.0-product-ctx-1-k` = 81 buckets, `key_padding_mask` on every call; models/transformer.py,
+ * rpe_attention_function.py:349-357) and every iRPE configuration with 64 < nb <= 128 buckets on k.
+ * `base` is a cream_irpe_attn_desc with the SAME meaning of every field, except that wherever that block says 64:
+ *   - the head width (q / k / v / out / dout / dq / dk / dv rows, the D of the tables (H', D, nb) / (H', nb, D)) is
+ *     head_dim;
+ *   - the width of the bucket-indexed side rows sv, lkg, gg, dlk, dlq — (B, H, NP, row_width) bf16 — is row_width,
+ *     and base.nb <= row_width.  Columns nb .. row_width - 1 of sv / dlk / dlq come out zero.
+ * Implemented: head_dim 32 | 64; row_width 64 with every subset of rpe on q / k / v (contextual or bias mode, shared
+ * or per-head tables), row_width 128 with rpe on k ALONE (wk or bk given; wq, bq, wv NULL).  Everything else —
+ * head_dim 48, nb > row_width, row_width 128 with a q or v table — returns CREAM_ERR_BAD_ARG and launches nothing.
+ * The bucket byte matrices are those of cream_irpe_bucket_bytes (they hold 2 * id: ids up to 127 fit). */
+typedef struct cream_irpe_attn2_desc {
+    cream_irpe_attn_desc base;
+    int32_t head_dim;               /* 32 | 64                                                            */
+    int32_t row_width;              /* 64 | 128                                                           */
+    /* key padding mask: (B, L) bytes, element (b, j) at key_pad[b*key_pad_sb + j]; non-zero = key j of image b takes
+     * no part for ANY query of that image: probability exactly 0, nothing added to lse, out, sv or a bucket gradient;
+     * dk = dv = 0 and a zero dlq row at that key, whatever its k / v rows hold.  Queries at padded positions attend
+     * to the real keys like every other query.  NULL: no mask.  PRECONDITION: at least one real key per image — an
+     * image whose keys are all masked gets non-finite out / lse rows (the reference gives NaN), without a fault.
+     * The SAME mask must be given to the backward call. */
+    const uint8_t* key_pad;
+    int64_t key_pad_sb;
+    /* out (fwd: written; bwd: read) and dout: element (b, n, h, :) at ptr[b*osb + n*osn + h*head_dim] resp.
+     * ptr[b*dosb + n*dosn + h*head_dim], so that sequence-first (L, N, E) tensors need no copy.  Multiples of 8.
+     * osb = osn = 0 (dosb = dosn = 0): contiguous (B, L, H, head_dim) as in the base block. */
+    int64_t osb, osn, dosb, dosn;
+} cream_irpe_attn2_desc;
+
+/* The argument check of the two calls below alone (backward != 0: of cream_irpe_attn2_bwd): CREAM_OK or the error
+ * code the call would return before launching.  Touches no device. */
+int cream_irpe_attn2_check(const cream_irpe_attn2_desc* d, int backward);
+
+/* out, lse (and sv) from q, k, v.  One launch.  Reads: q, k, v, tables, id* (query-major), key_pad. */
+int cream_irpe_attn2_fwd(const cream_irpe_attn2_desc* d, void* stream);
+
+/* dq, dk, dv and the bucket-gradient rows dlk, dlq from dout (+ out, lse, sv-independent).  Pre-pass (with wq): the
+ * (k * scale) Wq rows of all keys into dlq.  Launch A (lanes own queries) reads q, k, v, out, dout, lse, the
+ * query-major ids, key_pad and the pre-pass rows; writes delta, dq, dlk and the scratch rows lkg, gg.  Launch B (lanes
+ * own keys) reads q, k, v, dout, lse, delta, lkg, gg, the key-major ids (id*_t) and key_pad; writes dk, dv and, last,
+ * dlq.  delta, lkg, gg are scratch.  No global atomics: two calls on the same operands give the same bits. */
+int cream_irpe_attn2_bwd(const cream_irpe_attn2_desc* d, void* stream);
+
+/* cream_irpe_table_grad for the widths of the calls above: out[b*H+h][a][c] = mul * sum_n X[b,n,h][a] * Y[b,n,h][c],
+ * (xa x yc) fp32 per (b, h), xa / yc = the row widths of X / Y, each 32 | 64 | 128 (CREAM_ERR_BAD_ARG otherwise):
+ *   d lookup_table_weight(rpe_k) = (scale q)^T dlk  (head_dim x row_width), (rpe_q) = (scale k)^T dlq,
+ *   (rpe_v) = sv^T dout  (row_width x head_dim).  Rows of padded keys are zero in dlq; rows n >= L are not read. */
+int cream_irpe_table_grad2(float* out, const void* x, int64_t xsb, int64_t xsn, int64_t xsh, int xa, const void* y,
+                           int64_t ysb, int64_t ysn, int64_t ysh, int yc, int B, int H, int L, float mul, void* stream);
+
 /* ---- HBM-bound passes of one supernet transformer block ------------------------------------
  * Reference: TransformerEncoderLayer.forward, AutoFormer/model/supernet_transformer.py:251-287
  * (pre-norm block), LayerNormSuper.forward (model/module/layernorm_super.py:26-37), gelu in
