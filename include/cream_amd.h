@@ -236,7 +236,11 @@ int cream_tail_fwd(float* pooled, float* xm, float* part, float* mean, float* rs
 /* Backward of cream_tail_fwd given g = d loss / d pooled (B, E): dx (B*N, E) fp32 residual-stream gradient,
  * dx_scaled = bf16(sample_scale[b] * dx) (the gradient of f) and partial (cream_ln_partials(), E) = column
  * sums of dx_scaled (bias gradient of the projection that produced f).  gamma / beta gradients are
- * sum_b g * xm and sum_b g (caller). */
+ * sum_b g * xm and sum_b g (caller).  The class-token rows (n = 0) of dx and dx_scaled are exactly zero.  partial
+ * has cream_ln_partials() rows whatever B * N is: the rows of workgroups that had no row to walk are zeros.
+ * sample_scale (NULL = 1) multiplies dx_scaled whether or not f is given: with f == NULL cream_tail_fwd has nothing
+ * to scale and ignores it, while this call still writes bf16(sample_scale[b] * dx) — what the formula above says
+ * (tests/test_ends_gpu.py pins both). */
 int cream_tail_bwd(float* dx, void* dx_scaled, float* partial, const float* g, const float* x1, const void* f,
                    const float* mean, const float* rstd, const float* gamma, const float* sample_scale, int B, int N,
                    int E, void* stream);
