@@ -454,10 +454,35 @@ class JobTable:
         self.total = first[-1]
         self.jobs = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device)
         self.first = torch.tensor(first, dtype=torch.int32).to(device)
+        self._clip = None                    # (partials, out) of clip_coef, allocated on first use
 
-    def launch(self, update=False, lr=0.0, beta1=0.9, beta2=0.999, eps=1e-8, step=1):
-        _lib.check(_lib.load().cream_adamw_step(_p(self.jobs), _p(self.first), self.n, self.total, 1 if update else 0,
-                                                lr, beta1, beta2, eps, step, _stream()), "cream_adamw_step")
+    def launch(self, update=False, lr=0.0, beta1=0.9, beta2=0.999, eps=1e-8, step=1, coef=None):
+        """coef: a device float (`clip_coef(...)[1:]`) every gradient value is multiplied by as it is loaded — the clipped
+        step; the gradient tensors stay as they are."""
+        if coef is None:
+            _lib.check(_lib.load().cream_adamw_step(_p(self.jobs), _p(self.first), self.n, self.total, 1 if update else 0,
+                                                    lr, beta1, beta2, eps, step, _stream()), "cream_adamw_step")
+        else:
+            _lib.check(_lib.load().cream_adamw_step_clipped(_p(self.jobs), _p(self.first), self.n, self.total, 1 if update else 0,
+                                                            lr, beta1, beta2, eps, step, _p(coef), _stream()),
+                       "cream_adamw_step_clipped")
+
+    def clip_coef(self, max_norm):
+        """Global L2 norm of the table's gradients and the clip coefficient min(1, max_norm / (norm + 1e-6)) as a 2-float
+        device tensor {norm, coef} (the same tensor on every call) — two launches, no host synchronisation."""
+        if self._clip is None:
+            dev = self.jobs.device
+            self._clip = (torch.empty(max(self.total, 1), dtype=torch.float64, device=dev),
+                          torch.empty(2, dtype=torch.float32, device=dev))
+        partials, out = self._clip
+        _lib.check(_lib.load().cream_grad_clip_coef(_p(self.jobs), _p(self.first), self.n, self.total, float(max_norm),
+                                                    _p(partials), _p(out), _stream()), "cream_grad_clip_coef")
+        return out
+
+    def scale_grads(self, coef):
+        """g *= coef (a device float) in place over every gradient of the table."""
+        _lib.check(_lib.load().cream_grad_scale(_p(self.jobs), _p(self.first), self.n, self.total, _p(coef), _stream()),
+                   "cream_grad_scale")
 
 
 class BlockOperands:

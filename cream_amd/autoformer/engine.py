@@ -17,6 +17,7 @@ import random
 import torch
 import torch.nn.functional as F
 
+from .. import grad_clip as _grad_clip
 from . import block as _block
 from .supernet import Vision_TransformerSuper
 
@@ -99,6 +100,7 @@ class NativeAdamW(torch.optim.Optimizer):
         self._cream_rewrites_operands = True     # (block._register: no invalidation needed after this optimizer's step)
         self._steps = 0
         self._table = None
+        self.grad_norm = None                    # set by step(max_norm=...)
         self._grads = ()
         self._plist = ()
         self._ops = []
@@ -161,7 +163,11 @@ class NativeAdamW(torch.optim.Optimizer):
                      for g in self.param_groups for p in g['params'])
 
     @torch.no_grad()
-    def step(self, closure=None):
+    def step(self, closure=None, max_norm=None):
+        """max_norm: clip the global L2 norm of the gradients (torch.nn.utils.clip_grad_norm_, norm_type 2) inside the step —
+        one reduction over the job table, then the update multiplies every gradient value by the coefficient as it loads
+        it.  The `.grad` tensors are NOT scaled (the framework routine scales them in place).  `self.grad_norm` is the norm
+        before clipping as a 0-dim device tensor; reading it is the caller's synchronisation."""
         assert closure is None
         if (self._table is None or any(p.grad is not g for p, g in zip(self._plist, self._grads))
                 or self._ptrs != self._pointer_key()):
@@ -169,9 +175,13 @@ class NativeAdamW(torch.optim.Optimizer):
         g0 = self.param_groups[0]
         lr = g0['lr']
         assert all(g['lr'] == lr for g in self.param_groups), "NativeAdamW: one learning rate for all groups"
+        coef = None
+        if max_norm is not None:
+            out = self._table.clip_coef(max_norm)
+            self.grad_norm, coef = out[0], out[1:]
         self._steps += 1
         self._table.launch(update=True, lr=float(lr), beta1=g0['betas'][0], beta2=g0['betas'][1], eps=g0['eps'],
-                           step=self._steps)
+                           step=self._steps, coef=coef)
         for ops in self._ops:
             ops.mark_fresh()                 # the kernel rewrote every operand copy
 
@@ -248,9 +258,15 @@ class SupernetTrainer:
         if self.mixup_fn is not None:
             images, target = self.mixup_fn(images, target)
         loss = self.forward_backward(images, target)
-        if self.max_norm and self.max_norm > 0:
-            torch.nn.utils.clip_grad_norm_(self.model.parameters(), self.max_norm)
-        self.optimizer.step()                # (the native optimizer also rewrites the bf16 operand copies)
+        # (multi-rank: the norm is taken after reducer.finish() on the averaged gradients, and its summation order is fixed, so
+        # every rank computes the same coefficient without a collective)
+        clip = self.max_norm if self.max_norm and self.max_norm > 0 else None
+        if clip is not None and isinstance(self.optimizer, NativeAdamW):
+            self.optimizer.step(max_norm=clip)       # norm + clipped update on the device; .grad stays unscaled
+        else:
+            if clip is not None:
+                _grad_clip.clip_grad_norm_(self.model.parameters(), clip)
+            self.optimizer.step()            # (the native optimizer also rewrites the bf16 operand copies)
         return loss
 
 

@@ -28,24 +28,47 @@ using namespace cream;
 constexpr int TR = 96, TC = 64;                                 // tile: 96 rows (32 x the 3 qkv parts) x 64 columns
 constexpr int LP = TC + 2;                                      // LDS pitch (bf16) of the staged tile
 
-__global__ __launch_bounds__(256) void adamw_mirror_kernel(const cream_param_job* __restrict__ jobs,
-                                                           const int32_t* __restrict__ first_tile, int njobs, int update,
-                                                           float lr, float beta1, float beta2, float omb1, float omb2, float eps,
-                                                           float inv_bc1, float inv_sqrt_bc2)
+// "which job, which tile" of a workgroup, shared by every kernel of this file: the job is the last j with
+// first_tile[j] <= blockIdx.x, the tile the TR x TC one at (r0, c0) of the tensor viewed as rows x cols; a thread owns the 4
+// columns from c of the rows r0 + 16 k + rr, k < TR / 16.
+struct TileOfBlock {
+    cream_param_job jb;
+    int r0, c0, cq, rr, c;
+};
+
+__device__ __forceinline__ TileOfBlock tile_of_block(const cream_param_job* __restrict__ jobs, const int32_t* __restrict__ first_tile,
+                                                     int njobs)
 {
-    __shared__ uint16_t tile[TR * LP];
-    // job of this workgroup: last j with first_tile[j] <= blockIdx.x
     int lo = 0, hi = njobs - 1;
     while (lo < hi) {
         const int mid = (lo + hi + 1) >> 1;
         if (first_tile[mid] <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
     }
-    const cream_param_job jb = jobs[lo];
+    TileOfBlock w;
+    w.jb = jobs[lo];
     const int t = (int)blockIdx.x - first_tile[lo];
-    const int tcols = (jb.cols + TC - 1) / TC;
-    const int r0 = (t / tcols) * TR, c0 = (t % tcols) * TC;
-    const int tid = threadIdx.x, cq = tid & 15, rr = tid >> 4;  // 16 threads x 4 columns per row, 16 rows per pass
-    const int c = c0 + cq * 4;
+    const int tcols = (w.jb.cols + TC - 1) / TC;
+    w.r0 = (t / tcols) * TR;
+    w.c0 = (t % tcols) * TC;
+    w.cq = threadIdx.x & 15;                                    // 16 threads x 4 columns per row, 16 rows per pass
+    w.rr = threadIdx.x >> 4;
+    w.c = w.c0 + w.cq * 4;
+    return w;
+}
+
+// CLIP: every gradient value is multiplied by *coef (one fp32 multiply, what an in-place mul_ of the gradient in front of
+// the optimizer computes) as it is loaded; the gradient in memory stays as it is.
+template <bool CLIP>
+__global__ __launch_bounds__(256) void adamw_mirror_kernel(const cream_param_job* __restrict__ jobs,
+                                                           const int32_t* __restrict__ first_tile, int njobs, int update,
+                                                           float lr, float beta1, float beta2, float omb1, float omb2, float eps,
+                                                           float inv_bc1, float inv_sqrt_bc2, const float* __restrict__ coef)
+{
+    __shared__ uint16_t tile[TR * LP];
+    const TileOfBlock w = tile_of_block(jobs, first_tile, njobs);
+    const cream_param_job& jb = w.jb;
+    const int r0 = w.r0, c0 = w.c0, tid = threadIdx.x, cq = w.cq, rr = w.rr, c = w.c;
+    const float cf = CLIP ? *coef : 1.f;
     const bool upd = update && jb.g != nullptr;
     const float decay = 1.f - lr * jb.weight_decay, step = lr * inv_bc1;
     // three passes at a time: all twelve 16-byte loads of the three row groups are in flight before the first store (the parameter,
@@ -69,6 +92,7 @@ __global__ __launch_bounds__(256) void adamw_mirror_kernel(const cream_param_job
                     gv[u] = *reinterpret_cast<const f32x4v*>(jb.g + o[u]);
                     mv[u] = *reinterpret_cast<const f32x4v*>(jb.m + o[u]);
                     vv[u] = *reinterpret_cast<const f32x4v*>(jb.v + o[u]);
+                    if (CLIP) gv[u] *= cf;
                 }
             }
         }
@@ -96,7 +120,7 @@ __global__ __launch_bounds__(256) void adamw_mirror_kernel(const cream_param_job
                 for (int e = 0; e < nv; ++e) {
                     float p1 = jb.p[o[u] + e];
                     if (upd) {
-                        const float g1 = jb.g[o[u] + e];
+                        const float g1 = CLIP ? jb.g[o[u] + e] * cf : jb.g[o[u] + e];
                         float m1 = jb.m[o[u] + e], v1 = jb.v[o[u] + e];
                         p1 *= decay;
                         m1 = m1 + (g1 - m1) * omb1;
@@ -156,6 +180,132 @@ __global__ __launch_bounds__(256) void adamw_mirror_kernel(const cream_param_job
     }
 }
 
+// ---- global L2 norm of the gradients -> clip coefficient (torch.nn.utils.clip_grad_norm_, norm_type 2) -----------------
+// One partial per tile, no atomics: a thread sums the squares of its (at most 24) elements in fp32 in a fixed order, the
+// workgroup adds the 256 values in fp64 in a fixed order, grad_norm_finish_kernel adds the partials in index order.  The
+// result is a function of the inputs alone, not of workgroup scheduling: two launches on the same inputs give the same bits.
+__global__ __launch_bounds__(256) void grad_sqnorm_kernel(const cream_param_job* __restrict__ jobs,
+                                                          const int32_t* __restrict__ first_tile, int njobs,
+                                                          double* __restrict__ partials)
+{
+    __shared__ double wsum[4];
+    const TileOfBlock w = tile_of_block(jobs, first_tile, njobs);
+    const cream_param_job& jb = w.jb;
+    if (jb.g == nullptr) {                                      // (uniform over the workgroup)
+        if (threadIdx.x == 0) partials[blockIdx.x] = 0.0;
+        return;
+    }
+    const bool vec = (jb.ld & 3) == 0;
+    float s = 0.f;
+#pragma unroll
+    for (int pass0 = 0; pass0 < TR / 16; pass0 += 3) {
+        f32x4v gv[3];
+        bool fast[3], in[3];
+        int64_t o[3];
+#pragma unroll
+        for (int u = 0; u < 3; ++u) {
+            const int r = w.r0 + (pass0 + u) * 16 + w.rr;
+            in[u] = r < jb.rows && w.c < jb.cols;
+            o[u] = (int64_t)r * jb.ld + w.c;
+            fast[u] = in[u] && vec && w.c + 4 <= jb.cols;
+            gv[u] = f32x4v{0, 0, 0, 0};
+            if (fast[u]) gv[u] = *reinterpret_cast<const f32x4v*>(jb.g + o[u]);
+            else if (in[u]) {
+                const int nv = min(4, jb.cols - w.c);
+                for (int e = 0; e < nv; ++e) gv[u][e] = jb.g[o[u] + e];
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < 3; ++u)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) s += gv[u][e] * gv[u][e];       // (elements outside the tensor are +0: they add nothing)
+    }
+    double d = (double)s;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) d += __shfl_xor(d, off, 64);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = d;
+    __syncthreads();
+    if (threadIdx.x == 0) partials[blockIdx.x] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+}
+
+// out[0] = ||g||_2, out[1] = min(1, max_norm / (out[0] + 1e-6)) — torch.nn.utils.clip_grads_with_norm_.  One workgroup.
+__global__ __launch_bounds__(256) void grad_norm_finish_kernel(const double* __restrict__ partials, int n, double max_norm,
+                                                               float* __restrict__ out)
+{
+    __shared__ double part[256];
+    const int t = threadIdx.x;
+    double d = 0.0;
+    for (int i = t; i < n; i += 256) d += partials[i];
+    part[t] = d;
+    __syncthreads();
+#pragma unroll
+    for (int h = 128; h > 0; h >>= 1) {
+        if (t < h) part[t] += part[t + h];
+        __syncthreads();
+    }
+    if (t == 0) {
+        const float norm = (float)sqrt(part[0]);
+        const double q = max_norm / ((double)norm + 1e-6);
+        out[0] = norm;
+        out[1] = (float)(q < 1.0 ? q : (q != q ? q : 1.0));     // a NaN norm stays NaN, as under torch's clamp
+    }
+}
+
+// g *= *coef in place, for optimizers that are not ours.  coef == 1 (the common case late in training): no byte is loaded.
+__global__ __launch_bounds__(256) void grad_scale_kernel(const cream_param_job* __restrict__ jobs,
+                                                         const int32_t* __restrict__ first_tile, int njobs,
+                                                         const float* __restrict__ coef)
+{
+    const float cf = *coef;
+    if (cf == 1.f) return;
+    const TileOfBlock w = tile_of_block(jobs, first_tile, njobs);
+    const cream_param_job& jb = w.jb;
+    if (jb.g == nullptr) return;
+    float* g = const_cast<float*>(jb.g);
+    const bool vec = (jb.ld & 3) == 0;
+#pragma unroll
+    for (int pass0 = 0; pass0 < TR / 16; pass0 += 3) {
+        f32x4v gv[3];
+        bool fast[3], in[3];
+        int64_t o[3];
+#pragma unroll
+        for (int u = 0; u < 3; ++u) {
+            const int r = w.r0 + (pass0 + u) * 16 + w.rr;
+            in[u] = r < jb.rows && w.c < jb.cols;
+            o[u] = (int64_t)r * jb.ld + w.c;
+            fast[u] = in[u] && vec && w.c + 4 <= jb.cols;
+            if (fast[u]) gv[u] = *reinterpret_cast<const f32x4v*>(g + o[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < 3; ++u) {
+            if (fast[u]) {
+                gv[u] *= cf;
+                *reinterpret_cast<f32x4v*>(g + o[u]) = gv[u];
+            } else if (in[u]) {
+                const int nv = min(4, jb.cols - w.c);
+                for (int e = 0; e < nv; ++e) g[o[u] + e] = g[o[u] + e] * cf;
+            }
+        }
+    }
+}
+
+int launch_adamw(bool clip, const cream_param_job* jobs_dev, const int32_t* first_tile_dev, int njobs, int total_tiles, int update,
+                 double lr, double beta1, double beta2, double eps, int64_t step, const float* coef_dev, void* stream)
+{
+    if (njobs < 0 || total_tiles < 0 || (update && step < 1) || (clip && !coef_dev)) return CREAM_ERR_BAD_ARG;
+    if (njobs == 0 || total_tiles == 0) return CREAM_OK;
+    if (!jobs_dev || !first_tile_dev) return CREAM_ERR_BAD_ARG;
+    double bc1 = 1.0, bc2 = 1.0;
+    if (update) {
+        bc1 = 1.0 - pow(beta1, (double)step);
+        bc2 = 1.0 - pow(beta2, (double)step);
+    }
+    hipLaunchKernelGGL(clip ? adamw_mirror_kernel<true> : adamw_mirror_kernel<false>, dim3(total_tiles), dim3(256), 0,
+                       (hipStream_t)stream, jobs_dev, first_tile_dev, njobs, update, (float)lr, (float)beta1, (float)beta2,
+                       (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, (float)(1.0 / bc1), (float)(1.0 / sqrt(bc2)), coef_dev);
+    return hipGetLastError() == hipSuccess ? CREAM_OK : CREAM_ERR_LAUNCH;
+}
+
 }  // namespace
 
 extern "C" {
@@ -169,17 +319,37 @@ int cream_param_job_tiles(int rows, int cols)
 int cream_adamw_step(const cream_param_job* jobs_dev, const int32_t* first_tile_dev, int njobs, int total_tiles, int update,
                      double lr, double beta1, double beta2, double eps, int64_t step, void* stream)
 {
-    if (njobs < 0 || total_tiles < 0 || (update && step < 1)) return CREAM_ERR_BAD_ARG;
+    return launch_adamw(false, jobs_dev, first_tile_dev, njobs, total_tiles, update, lr, beta1, beta2, eps, step, nullptr, stream);
+}
+
+int cream_adamw_step_clipped(const cream_param_job* jobs_dev, const int32_t* first_tile_dev, int njobs, int total_tiles, int update,
+                             double lr, double beta1, double beta2, double eps, int64_t step, const float* coef_dev, void* stream)
+{
+    return launch_adamw(true, jobs_dev, first_tile_dev, njobs, total_tiles, update, lr, beta1, beta2, eps, step, coef_dev, stream);
+}
+
+int cream_grad_clip_coef(const cream_param_job* jobs_dev, const int32_t* first_tile_dev, int njobs, int total_tiles,
+                         double max_norm, double* partials_dev, float* out_dev, void* stream)
+{
+    if (njobs < 0 || total_tiles < 0 || !out_dev || !(max_norm > 0.0)) return CREAM_ERR_BAD_ARG;
+    if (njobs > 0 && (!jobs_dev || !first_tile_dev)) return CREAM_ERR_BAD_ARG;
+    const int n = njobs > 0 ? total_tiles : 0;
+    if (n > 0 && !partials_dev) return CREAM_ERR_BAD_ARG;
+    if (n > 0)
+        hipLaunchKernelGGL(grad_sqnorm_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, jobs_dev, first_tile_dev, njobs,
+                           partials_dev);
+    hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials_dev, n, max_norm, out_dev);
+    return hipGetLastError() == hipSuccess ? CREAM_OK : CREAM_ERR_LAUNCH;
+}
+
+int cream_grad_scale(const cream_param_job* jobs_dev, const int32_t* first_tile_dev, int njobs, int total_tiles,
+                     const float* coef_dev, void* stream)
+{
+    if (njobs < 0 || total_tiles < 0 || !coef_dev) return CREAM_ERR_BAD_ARG;
     if (njobs == 0 || total_tiles == 0) return CREAM_OK;
     if (!jobs_dev || !first_tile_dev) return CREAM_ERR_BAD_ARG;
-    double bc1 = 1.0, bc2 = 1.0;
-    if (update) {
-        bc1 = 1.0 - pow(beta1, (double)step);
-        bc2 = 1.0 - pow(beta2, (double)step);
-    }
-    hipLaunchKernelGGL(adamw_mirror_kernel, dim3(total_tiles), dim3(256), 0, (hipStream_t)stream, jobs_dev, first_tile_dev, njobs,
-                       update, (float)lr, (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, (float)(1.0 / bc1),
-                       (float)(1.0 / sqrt(bc2)));
+    hipLaunchKernelGGL(grad_scale_kernel, dim3(total_tiles), dim3(256), 0, (hipStream_t)stream, jobs_dev, first_tile_dev, njobs,
+                       coef_dev);
     return hipGetLastError() == hipSuccess ? CREAM_OK : CREAM_ERR_LAUNCH;
 }
 

@@ -18,6 +18,7 @@ import math
 import torch
 import torch.nn.functional as F
 
+from .. import grad_clip
 from .soft_loss import ClipSoftLoss, gather_features_with_grad
 
 
@@ -63,6 +64,7 @@ class DistillStep:
             p.requires_grad = False
         teacher.eval()
         self.params = [p for p in student.parameters() if p.requires_grad]
+        self.last_grad_norm = None
 
     def _autocast(self, device):
         on = self.amp_dtype != torch.float32 and device.type == "cuda"
@@ -104,7 +106,7 @@ class DistillStep:
             assert self.reducer.owns_grads(), "a parameter gradient no longer aliases the reducer's arena"
             self.reducer.finish()
         if self.clip is not None:
-            torch.nn.utils.clip_grad_norm_(self.params, self.clip, norm_type=2.0)
+            self.last_grad_norm = grad_clip.clip_grad_norm_(self.params, self.clip)    # train.py:500 logs it (a device tensor)
         self.optimizer.step()
         with torch.no_grad():                                                              # train.py:526-530
             if self.logit_scale is not None:

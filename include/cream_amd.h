@@ -554,6 +554,27 @@ int cream_param_job_tiles(int rows, int cols);
 int cream_adamw_step(const cream_param_job* jobs_dev, const int32_t* first_tile_dev, int njobs, int total_tiles,
                      int update, double lr, double beta1, double beta2, double eps, int64_t step, void* stream);
 
+/* Global-norm gradient clipping (torch.nn.utils.clip_grad_norm_, norm_type 2) over the same job table, without a host
+ * synchronisation and without a second pass over the gradients:
+ *     out[0] = sqrt(sum over every job with g != NULL of g[r, c]^2),   r < rows, c < cols (columns cols..ld are never read)
+ *     out[1] = min(1, max_norm / (out[0] + 1e-6))                      (torch.nn.utils.clip_grads_with_norm_)
+ * max_norm > 0; +inf gives the norm alone (out[1] = 1).  A non-finite norm propagates as in torch (inf -> 0, NaN -> NaN).
+ * The summation order is fixed — fp32 over a thread's at most 24 elements, fp64 over the workgroup into partials_dev[tile],
+ * fp64 over the partials in index order — so the result is bit-reproducible and independent of scheduling; every entry of
+ * partials_dev (total_tiles doubles) is rewritten by every call.  With no tiles out = {0, 1}.
+ * cream_adamw_step_clipped is cream_adamw_step with every gradient value multiplied by *coef_dev (one fp32 multiply) as it
+ * is loaded: the gradient tensors themselves are NOT modified (torch's clip_grad_norm_ scales them in place).
+ * cream_grad_scale does scale them in place (g *= *coef_dev), for an optimizer that is not cream_adamw_step; with
+ * *coef_dev == 1 nothing is read or written.
+ * cream_grad_clip_coef and cream_grad_scale read only g, rows, cols and ld of a job: p (and m, v, the copies) may be NULL. */
+int cream_grad_clip_coef(const cream_param_job* jobs_dev, const int32_t* first_tile_dev, int njobs, int total_tiles,
+                         double max_norm, double* partials_dev, float* out_dev, void* stream);
+int cream_adamw_step_clipped(const cream_param_job* jobs_dev, const int32_t* first_tile_dev, int njobs, int total_tiles,
+                             int update, double lr, double beta1, double beta2, double eps, int64_t step,
+                             const float* coef_dev, void* stream);
+int cream_grad_scale(const cream_param_job* jobs_dev, const int32_t* first_tile_dev, int njobs, int total_tiles,
+                     const float* coef_dev, void* stream);
+
 /* Gradient finalisation for the weight-entangled parameters: every tensor of a block gets
  *     dst[map(r)*ld + c] += sum_p src[p*pstride + r*cols + c]          r < rows, c < cols
  * in ONE launch — dst is the ACTIVE SLICE W[:out, :in] of the fp32 super-weight gradient

@@ -20,7 +20,7 @@ def category(k):
         return "GEMM library (hipBLASLt)"
     if "gemm_nt_kernel" in k or "gemm_tn_kernel" in k or "gemm_nt8_kernel" in k or "gemm_tn8_kernel" in k:
         return "GEMM (csrc/gemm_mfma.hpp, gemm_nt8.hpp, gemm_tn8.hpp: hand-written MFMA)"
-    if "adamw_mirror" in k:
+    if "adamw_mirror" in k or "grad_sqnorm" in k or "grad_norm_finish" in k or "grad_scale_kernel" in k:
         return "optimizer + bf16 operand refresh (csrc/optim.hip)"
     if "attn_rpe2d" in k:
         return "attention (csrc/attn_rpe2d.hip)"
