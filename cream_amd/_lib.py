@@ -54,6 +54,8 @@ SIGNATURES = {
     "cream_irpe_attn2_fwd": (_i, [_vp, _vp]),
     "cream_irpe_attn2_bwd": (_i, [_vp, _vp]),
     "cream_irpe_table_grad2": (_i, [_vp, _vp, _i64, _i64, _i64, _i, _vp, _i64, _i64, _i64, _i, _i, _i, _i, _f, _vp]),
+    "cream_mini_attn_fwd": (_i, [_vp, _vp]),
+    "cream_mini_attn_bwd": (_i, [_vp, _vp]),
     "cream_attn_rpe2d_padded_len": (_i, [_i]),
     "cream_attn_rpe2d_dtab_parts": (_i, [_i, _i]),
     "cream_attn_rpe2d_bwd_mode": (_i, [_i]),
@@ -199,6 +201,16 @@ class IrpeAttn2Desc(ctypes.Structure):
     """struct cream_irpe_attn2_desc of include/cream_amd.h."""
     _fields_ = ([("base", IrpeAttnDesc), ("head_dim", _c.c_int32), ("row_width", _c.c_int32), ("key_pad", _vp)] +
                 [(n, _i64) for n in ("key_pad_sb", "osb", "osn", "dosb", "dosn")])
+
+
+class MiniAttnDesc(ctypes.Structure):
+    """struct cream_mini_attn_desc of include/cream_amd.h."""
+    _fields_ = ([(n, _vp) for n in ("q", "k", "v")] + [(n, _i64) for n in ("sb", "sn", "sh")] +
+                [(n, _vp) for n in ("out", "lse", "wk")] + [("wk_hs", _i64)] +
+                [(n, _vp) for n in ("idk", "idk_t", "wl", "ww")] +
+                [(n, _c.c_int32) for n in ("B", "H", "L", "NP", "nb", "head_dim")] + [("scale", _f), ("reserved", _c.c_int32)] +
+                [(n, _vp) for n in ("dout", "dq", "dk", "dv")] + [(n, _i64) for n in ("dsb", "dsn", "dsh")] +
+                [(n, _vp) for n in ("delta", "lkg", "dlk", "dwl_part", "dww_part")])
 
 
 class ParamJob(ctypes.Structure):

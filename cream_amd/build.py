@@ -61,7 +61,8 @@ def is_current():
 # the default AGPR form the compiler copies every score tile AGPR -> VGPR (240 v_accvgpr moves per
 # iteration in the fused iRPE forward) and the AGPR half of the register file caps occupancy
 EXTRA_FLAGS = {"irpe_attn.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
-               "irpe_attn_x.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}
+               "irpe_attn_x.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
+               "mini_attn.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}
 
 
 def build(force=False, verbose=False):

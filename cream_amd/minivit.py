@@ -13,8 +13,12 @@ weight`), so Mini-DeiT checkpoints load.
 Two paths through `MiniAttention.forward`:
   * without head transforms the attention core is exactly `RPEAttention`'s: the fused kernels (csrc/irpe_attn.hip)
     take it under bf16 autocast, with the tables of the current repeat;
-  * with head transforms every head's (L, L) map is needed at once (the convolutions contract over heads), so the
-    map is formed: q k^T + HIP `rpe_index` gathers, conv_l, softmax, conv_w, P v + bucket sums.
+  * with head transforms the convolutions contract over heads at one (query, key) position, so a (query tile x key
+    tile) block that carries all heads is self-contained: under bf16 autocast, with rpe on k only (or none), head_dim 64
+    and at most 12 heads — every published Mini-DeiT — the fused kernels of csrc/mini_attn.hip take it
+    (cream_amd.mini_attn), with the tables and convolutions of the current repeat;
+  * everything else (fp32, rpe on q / v, active attention dropout, ...) forms the map: q k^T + HIP `rpe_index`
+    gathers, conv_l, softmax, conv_w, P v + bucket sums.
 
 Deviation: with `repeated_times == 1` the reference's `MiniBlock` defines no `norm1` / `norm2` (:146-148) and its
 forward raises AttributeError; here that case gets plain LayerNorms (the block is then an `RPEBlock`).
@@ -24,7 +28,7 @@ from functools import partial
 import torch
 import torch.nn as nn
 
-from . import irpe_fused
+from . import irpe_fused, mini_attn
 from .irpe import build_rpe, get_rpe_config
 from .rpe_attention import DropPath, Mlp, PatchEmbed
 
@@ -99,6 +103,12 @@ class MiniAttention(nn.Module):
             out = irpe_fused.attention(qkv.view(B, N, 3, self.num_heads, hd), self.scale, rq, rk, rv,
                                        dropout_p=self.attn_drop.p if self.training else 0.0)
             return self.proj_drop(self.proj(out))
+        if self.conv_l is not None:
+            wl, ww = self.conv_l.current().weight, self.conv_w.current().weight
+            if mini_attn.usable_mixed(qkv.dtype, qkv.device, hd, self.num_heads, N, (rq, rk, rv), wl, ww,
+                                      dropout_p=self.attn_drop.p if self.training else 0.0):
+                out = mini_attn.attention_mixed(qkv.view(B, N, 3, self.num_heads, hd), self.scale, rk, wl, ww)
+                return self.proj_drop(self.proj(out))
         q, k, v = qkv.reshape(B, N, 3, self.num_heads, hd).permute(2, 0, 3, 1, 4).unbind(0)
         q = q * self.scale                                   # :88
         attn = q @ k.transpose(-2, -1)

@@ -312,6 +312,44 @@ int cream_irpe_attn_bwd(const cream_irpe_attn_desc* d, void* stream);
 int cream_irpe_table_grad(float* out, const void* x, int64_t xsb, int64_t xsn, int64_t xsh, const void* y, int64_t ysb,
                           int64_t ysn, int64_t ysh, int B, int H, int L, float mul, void* stream);
 
+/* ---- fused Mini-DeiT attention: head-mixing 1x1 convolutions before (wl) and after (ww) the softmax ------------
+ * MiniAttention.forward with use_transform (MiniViT/Mini-DeiT/mini_vision_transformer.py:84-114) between the qkv and
+ * proj linears — see csrc/mini_attn.hip for the formulas:
+ *     S_h = (s q_h) k_h^T + rpe_k lookups,  S'_o = sum_h wl[o,h] S_h,  P_o = softmax(S'_o),  P'_o = sum_h ww[o,h] P_h,
+ *     O_o = P'_o v_o.
+ * bf16 operands, fp32 accumulation, head_dim 64, 1 <= H <= 12, L <= 2048, contextual rpe on k with at most 64 buckets
+ * (wk == NULL: none).  Fields named as in cream_irpe_attn_desc mean the same; lse is the log-sum-exp of the MIXED
+ * logits S'.  Anything else (H > 12, head_dim != 64, nb > 64, a missing wl or ww) returns CREAM_ERR_BAD_ARG before any
+ * HIP call.  Nothing of size L^2 is written; no global atomics: the two H x H weight gradients come as one partial
+ * per workgroup, (B * NP / 32, H, H) fp32 each, [out][in] like the weights, which the caller sums over the first axis. */
+typedef struct cream_mini_attn_desc {
+    const void *q, *k, *v;          /* bf16; element (b, n, h, :) at ptr[b*sb + n*sn + h*sh]            */
+    int64_t sb, sn, sh;
+    void* out;                      /* (B, L, H, 64) bf16 (fwd only: the backward does not read it)    */
+    float* lse;                     /* (B, H, L) (fwd: out, bwd: in)                                     */
+    const float* wk;                /* lookup_table_weight of rpe_k (H', 64, nb) or NULL                 */
+    int64_t wk_hs;                  /* element stride between heads, 0 for shared_head                   */
+    const uint8_t *idk, *idk_t;     /* (NP, NP) cream_irpe_bucket_bytes matrices, query- / key-major (bwd) */
+    const float *wl, *ww;           /* (H, H) fp32, [out][in]: conv_l / conv_w weight[:, :, 0, 0]        */
+    int32_t B, H, L, NP, nb, head_dim;
+    float scale;
+    int32_t reserved;
+    /* backward only */
+    const void* dout;               /* (B, L, H, 64) bf16                                               */
+    void *dq, *dk, *dv;             /* bf16; element (b, n, h, :) at ptr[b*dsb + n*dsn + h*dsh]          */
+    int64_t dsb, dsn, dsh;
+    float* delta;                   /* (B, H, NP) scratch                                               */
+    void *lkg, *dlk;                /* (B, H, NP, 64) bf16: scratch / out (bucket gradients of the rpe_k lookups;
+                                       d lookup_table_weight = cream_irpe_table_grad(q, dlk, mul = scale)) */
+    float *dwl_part, *dww_part;     /* (B * NP / 32, H, H) fp32 out                                      */
+} cream_mini_attn_desc;
+
+/* out and lse from q, k, v.  One launch (two passes over the keys inside). */
+int cream_mini_attn_fwd(const cream_mini_attn_desc* d, void* stream);
+
+/* dq, dk, dv, the dlk rows and the partials of d wl / d ww from dout and lse.  2 + ceil(H / 4) launches. */
+int cream_mini_attn_bwd(const cream_mini_attn_desc* d, void* stream);
+
 /* ---- fused iRPE attention, generalised: 32- or 64-wide heads, up to 128 buckets, key padding mask -------------
  * The same operator as cream_irpe_attn_fwd / _bwd (same formulas, launches and conventions; csrc/irpe_attn_x.hip),
  * for the callers those entry points refuse: DETR-with-iRPE's encoder self-attention (d_model 256 / 8 heads = 32,
