@@ -56,6 +56,11 @@ SIGNATURES = {
     "cream_irpe_table_grad2": (_i, [_vp, _vp, _i64, _i64, _i64, _i, _vp, _i64, _i64, _i64, _i, _i, _i, _i, _f, _vp]),
     "cream_mini_attn_fwd": (_i, [_vp, _vp]),
     "cream_mini_attn_bwd": (_i, [_vp, _vp]),
+    "cream_window_attn_check": (_i, [_vp, _i]),
+    "cream_window_attn_part_size": (_i, [_i, _i, _i]),
+    "cream_window_attn_blocks": (_i, [_vp]),
+    "cream_window_attn_fwd": (_i, [_vp, _vp]),
+    "cream_window_attn_bwd": (_i, [_vp, _vp]),
     "cream_attn_rpe2d_padded_len": (_i, [_i]),
     "cream_attn_rpe2d_dtab_parts": (_i, [_i, _i]),
     "cream_attn_rpe2d_bwd_mode": (_i, [_i]),
@@ -211,6 +216,16 @@ class MiniAttnDesc(ctypes.Structure):
                 [(n, _c.c_int32) for n in ("B", "H", "L", "NP", "nb", "head_dim")] + [("scale", _f), ("reserved", _c.c_int32)] +
                 [(n, _vp) for n in ("dout", "dq", "dk", "dv")] + [(n, _i64) for n in ("dsb", "dsn", "dsh")] +
                 [(n, _vp) for n in ("delta", "lkg", "dlk", "dwl_part", "dww_part")])
+
+
+class WindowAttnDesc(ctypes.Structure):
+    """struct cream_window_attn_desc of include/cream_amd.h."""
+    _fields_ = ([(n, _vp) for n in ("q", "k", "v")] + [(n, _i64) for n in ("sb", "sn", "sh")] +
+                [(n, _vp) for n in ("out", "lse", "table", "wl", "bl", "ww", "bw")] +
+                [(n, _c.c_int32) for n in ("B", "H", "Hs", "Ws", "w", "shift", "mask_shift", "head_dim")] +
+                [("scale", _f), ("part_blocks", _c.c_int32)] +
+                [(n, _vp) for n in ("dout", "dq", "dk", "dv")] + [(n, _i64) for n in ("dsb", "dsn", "dsh")] +
+                [(n, _vp) for n in ("delta", "part")])
 
 
 class ParamJob(ctypes.Structure):

@@ -1,0 +1,437 @@
+"""Mini-Swin (weight-shared Swin Transformer with per-repeat LayerNorms, head transforms and local convolutions) —
+host-side mirror of MiniViT/Mini-Swin/models/swin_transformer_minivit.py (`WindowAttention` :59-163,
+`SwinTransformerBlock` :166-396, `PatchMerging` :399-445, `BasicLayer` :448-534, `PatchEmbed` :537-582,
+`SwinTransformerMiniViT` :585-732) on the fused window attention of cream_amd.window_attn.  With the three MiniViT flags
+off and `separate_layer_num_list` = depths it is the plain Swin Transformer of the same directory (the distillation teacher).
+
+One `SwinTransformerBlock` (qkv, proj, Mlp, the bias table: the shared weights) runs `share_num` times in a row, the
+cyclic shift alternating from `is_init_window_shift`; what is NOT shared is picked by the repeat index: the LayerNorms
+(`norm1_list`, `norm2_list`), the two nn.Linear(H, H) over the heads of the attention map (`proj_l` before the softmax,
+`proj_w` after it), the LayerNorm + depthwise 7x7 convolution between attention and MLP (`local_norm_list`,
+`local_conv_list`) and the drop-path rate.  Same constructor arguments, parameter and buffer names as the reference
+(`layers.{i}.blocks.{j}.attn.relative_position_bias_table`, `...attn.relative_position_index`, `...attn_mask`,
+`...norm1_list.{r}.weight`, `...proj_l.{r}.weight`), so Mini-Swin checkpoints load.
+
+As in the reference, a block whose map is larger than the window always has `shift_size = window_size // 2` and its
+`attn_mask` is passed to the attention in EVERY repeat, rolled or not.
+
+Two paths through `SwinTransformerBlock.forward_feature`:
+  * fused — under bf16 autocast on a device where `window_attn.usable_window` agrees: norm1 -> qkv on (B, L, C) ->
+    `window_attn.window_attention` -> proj; no roll, no partition, no (N, N) map;
+  * composed — everything else (fp32, CPU, window 12, active attention dropout, more than 16 mixed heads): the
+    reference's arithmetic step by step.
+The depthwise local convolution, patch merging and patch embedding stay with the framework.
+"""
+import torch
+import torch.nn as nn
+
+from . import window_attn
+from .rpe_attention import DropPath
+
+
+def _pair(x):
+    return tuple(x) if isinstance(x, (tuple, list)) else (x, x)
+
+
+def _trunc_normal(t, std=.02):
+    return nn.init.trunc_normal_(t, std=std, a=-2., b=2.)
+
+
+class Mlp(nn.Module):
+    """:7-24."""
+
+    def __init__(self, in_features, hidden_features=None, out_features=None, act_layer=nn.GELU, drop=0.):
+        super().__init__()
+        out_features = out_features or in_features
+        hidden_features = hidden_features or in_features
+        self.fc1 = nn.Linear(in_features, hidden_features)
+        self.act = act_layer()
+        self.fc2 = nn.Linear(hidden_features, out_features)
+        self.drop = nn.Dropout(drop)
+
+    def forward(self, x):
+        return self.drop(self.fc2(self.drop(self.act(self.fc1(x)))))
+
+
+def window_partition(x, window_size):
+    """(B, H, W, C) -> (B * nW, w, w, C), windows row-major (:27-39)."""
+    B, H, W, C = x.shape
+    x = x.view(B, H // window_size, window_size, W // window_size, window_size, C)
+    return x.permute(0, 1, 3, 2, 4, 5).reshape(-1, window_size, window_size, C)
+
+
+def window_reverse(windows, window_size, H, W):
+    """(B * nW, w, w, C) -> (B, H, W, C) (:42-56)."""
+    B = windows.shape[0] // ((H // window_size) * (W // window_size))
+    x = windows.view(B, H // window_size, W // window_size, window_size, window_size, -1)
+    return x.permute(0, 1, 3, 2, 4, 5).reshape(B, H, W, -1)
+
+
+def relative_position_index(wh, ww):
+    """(wh*ww, wh*ww) table row of every (query, key) pair: (iy-jy+wh-1)(2ww-1) + (ix-jx+ww-1) (:94-103)."""
+    ys, xs = torch.meshgrid(torch.arange(wh), torch.arange(ww), indexing="ij")
+    ys, xs = ys.flatten(), xs.flatten()
+    return (ys[:, None] - ys[None, :] + wh - 1) * (2 * ww - 1) + (xs[:, None] - xs[None, :] + ww - 1)
+
+
+def shift_mask(H, W, window_size, shift_size):
+    """(nW, N, N) of {0, -100}: tokens of one window that come from different regions of the rolled map (:233-252)."""
+    img = torch.zeros((1, H, W, 1))
+    cuts = (slice(0, -window_size), slice(-window_size, -shift_size), slice(-shift_size, None))
+    n = 0
+    for hs in cuts:
+        for ws in cuts:
+            img[:, hs, ws, :] = n
+            n += 1
+    ids = window_partition(img, window_size).view(-1, window_size * window_size)
+    diff = ids.unsqueeze(1) - ids.unsqueeze(2)
+    return torch.where(diff != 0, torch.full_like(diff, -100.0), torch.zeros_like(diff))
+
+
+class WindowAttention(nn.Module):
+    """:59-163.  `forward` is the composed path on partitioned windows; `forward_map` the fused one on the whole map."""
+
+    def __init__(self, dim, window_size, num_heads, qkv_bias=True, qk_scale=None, attn_drop=0., proj_drop=0.):
+        super().__init__()
+        self.dim = dim
+        self.window_size = _pair(window_size)
+        self.num_heads = num_heads
+        head_dim = dim // num_heads
+        self.scale = qk_scale or head_dim ** -0.5
+        self.qkv = nn.Linear(dim, dim * 3, bias=qkv_bias)
+        self.attn_drop = nn.Dropout(attn_drop)
+        self.proj = nn.Linear(dim, dim)
+        self.proj_drop = nn.Dropout(proj_drop)
+        self.softmax = nn.Softmax(dim=-1)
+        wh, ww = self.window_size
+        self.relative_position_bias_table = nn.Parameter(torch.zeros((2 * wh - 1) * (2 * ww - 1), num_heads))
+        self.register_buffer("relative_position_index", relative_position_index(wh, ww))
+        _trunc_normal(self.relative_position_bias_table)
+
+    def usable(self, qkv, window_size, proj_l, proj_w):
+        """Whether the fused kernels take this call (window_size: the block's, which a small map may have clamped)."""
+        if self.window_size[0] != self.window_size[1] or window_size != self.window_size[0]:
+            return False
+        return window_attn.usable_window(qkv.dtype, qkv.device, self.dim // self.num_heads, self.num_heads, window_size,
+                                         self.relative_position_bias_table, proj_l, proj_w,
+                                         dropout_p=self.attn_drop.p if self.training else 0.0)
+
+    def forward_map(self, qkv, geometry, proj_l=None, proj_w=None):
+        """qkv (B, Hs*Ws, 3C) of the unshifted map -> (B, Hs*Ws, C) after proj, through the fused kernels."""
+        B, L, _ = qkv.shape
+        out = window_attn.window_attention(qkv.view(B, L, 3, self.num_heads, self.dim // self.num_heads), self.scale,
+                                           self.relative_position_bias_table, geometry, proj_l, proj_w)
+        return self.proj_drop(self.proj(out))
+
+    def forward(self, x, mask=None, proj_l=None, proj_w=None):
+        B_, N, C = x.shape
+        return self.attend(self.qkv(x), mask, proj_l, proj_w)
+
+    def attend(self, qkv, mask=None, proj_l=None, proj_w=None):
+        """The reference's arithmetic on partitioned windows: qkv (B * nW, N, 3C) -> (B * nW, N, C) after proj."""
+        B_, N, C3 = qkv.shape
+        C = C3 // 3
+        q, k, v = qkv.reshape(B_, N, 3, self.num_heads, C // self.num_heads).permute(2, 0, 3, 1, 4).unbind(0)
+        attn = (q * self.scale) @ k.transpose(-2, -1)
+        bias = self.relative_position_bias_table[self.relative_position_index.view(-1)].view(N, N, -1)
+        attn = attn + bias.permute(2, 0, 1).unsqueeze(0)
+        if proj_l is not None:
+            attn = proj_l(attn.permute(0, 2, 3, 1)).permute(0, 3, 1, 2)
+        if mask is not None:
+            nW = mask.shape[0]
+            attn = (attn.view(B_ // nW, nW, self.num_heads, N, N) + mask.unsqueeze(1).unsqueeze(0)).view(-1, self.num_heads, N, N)
+        attn = self.softmax(attn)
+        if proj_w is not None:
+            attn = proj_w(attn.permute(0, 2, 3, 1)).permute(0, 3, 1, 2)
+        attn = self.attn_drop(attn)
+        x = (attn @ v).transpose(1, 2).reshape(B_, N, C)
+        return self.proj_drop(self.proj(x))
+
+    def extra_repr(self):
+        return f'dim={self.dim}, window_size={self.window_size}, num_heads={self.num_heads}'
+
+
+class SwinTransformerBlock(nn.Module):
+    """:166-396."""
+
+    def __init__(self, dim, input_resolution, num_heads, window_size=7, mlp_ratio=4., qkv_bias=True, qk_scale=None, drop=0.,
+                 attn_drop=0., shift_size=0., drop_path=(0,), act_layer=nn.GELU, norm_layer=nn.LayerNorm,
+                 is_init_window_shift=False, is_sep_layernorm=False, is_transform_FFN=False, is_transform_heads=False):
+        super().__init__()
+        self.dim = dim
+        self.input_resolution = input_resolution
+        self.num_heads = num_heads
+        self.window_size = window_size
+        self.mlp_ratio = mlp_ratio
+        self.share_num = len(drop_path)
+        self.is_init_window_shift = is_init_window_shift
+        self.is_sep_layernorm = is_sep_layernorm
+        self.is_transform_FFN = is_transform_FFN
+        self.is_transform_heads = is_transform_heads
+
+        def per_repeat(make):
+            return nn.ModuleList([make() for _ in range(self.share_num)])
+
+        if is_sep_layernorm:
+            self.norm1_list = per_repeat(lambda: norm_layer(dim))
+        else:
+            self.norm1 = norm_layer(dim)
+        if is_transform_heads:
+            self.proj_l = nn.ModuleList()
+            self.proj_w = nn.ModuleList()
+            for _ in range(self.share_num):                 # creation order of the reference: l, w, l, w, ...
+                self.proj_l.append(nn.Linear(num_heads, num_heads))
+                self.proj_w.append(nn.Linear(num_heads, num_heads))
+        else:
+            self.proj_l = self.proj_w = None
+        self.attn = WindowAttention(dim, window_size=_pair(window_size), num_heads=num_heads, qkv_bias=qkv_bias, qk_scale=qk_scale,
+                                    attn_drop=attn_drop, proj_drop=drop)
+        if min(input_resolution) <= self.window_size:        # the map is one window: no partition, no shift (:227-230)
+            shift_size = 0
+            self.window_size = min(input_resolution)
+        assert 0 <= shift_size < self.window_size, "shift_size must in 0-window_size"
+        self.shift_size = int(shift_size)
+        self.register_buffer("attn_mask", shift_mask(*input_resolution, self.window_size, self.shift_size)
+                             if self.shift_size > 0 else None)
+        if is_sep_layernorm:
+            self.norm2_list = per_repeat(lambda: norm_layer(dim))
+        else:
+            self.norm2 = norm_layer(dim)
+        self.mlp = Mlp(in_features=dim, hidden_features=int(dim * mlp_ratio), act_layer=act_layer, drop=drop)
+        self.drop_path = nn.ModuleList([DropPath(p) if p > 0. else nn.Identity() for p in drop_path])
+        if is_transform_FFN:
+            self.local_norm_list = nn.ModuleList()
+            self.local_conv_list = nn.ModuleList()
+            for _ in range(self.share_num):
+                self.local_norm_list.append(norm_layer(dim))
+                self.local_conv_list.append(nn.Conv2d(dim, dim, 7, 1, 3, groups=dim, bias=qkv_bias))
+        else:
+            self.local_conv_list = None
+
+    def forward_feature(self, x, is_shift=False, layer_index=0):
+        H, W = self.input_resolution
+        B, L, C = x.shape
+        assert L == H * W, "input feature has wrong size"
+        shortcut = x
+        x = (self.norm1_list[layer_index] if self.is_sep_layernorm else self.norm1)(x)
+        proj_l = self.proj_l[layer_index] if self.is_transform_heads else None
+        proj_w = self.proj_w[layer_index] if self.is_transform_heads else None
+        shift = self.shift_size if is_shift else 0
+        w = self.window_size
+        qkv = self.attn.qkv(x)                               # per token: commutes with the roll and the partition
+        if self.attn.usable(qkv, w, proj_l, proj_w):
+            x = self.attn.forward_map(qkv, (H, W, w, shift, self.shift_size), proj_l, proj_w)
+        else:
+            qkv = qkv.view(B, H, W, 3 * C)
+            if shift > 0:
+                qkv = torch.roll(qkv, shifts=(-shift, -shift), dims=(1, 2))
+            windows = window_partition(qkv, w).reshape(-1, w * w, 3 * C)
+            x = self.attn.attend(windows, mask=self.attn_mask, proj_l=proj_l, proj_w=proj_w)      # the mask in every repeat (:312)
+            x = window_reverse(x.view(-1, w, w, C), w, H, W)
+            if shift > 0:
+                x = torch.roll(x, shifts=(shift, shift), dims=(1, 2))
+            x = x.reshape(B, H * W, C)
+        x = shortcut + self.drop_path[layer_index](x)
+        if self.local_conv_list is not None:
+            x = self.local_norm_list[layer_index](x)
+            x = x.permute(0, 2, 1).reshape(B, C, H, W)
+            x = x + self.local_conv_list[layer_index](x)
+            x = x.reshape(B, C, H * W).permute(0, 2, 1)
+        norm2 = self.norm2_list[layer_index] if self.is_sep_layernorm else self.norm2
+        return x + self.drop_path[layer_index](self.mlp(norm2(x)))
+
+    def forward(self, x):
+        shift = self.is_init_window_shift
+        for index in range(self.share_num):
+            x = self.forward_feature(x, shift, index)
+            shift = not shift
+        return x
+
+    def extra_repr(self):
+        return (f"dim={self.dim}, input_resolution={self.input_resolution}, num_heads={self.num_heads}, "
+                f"window_size={self.window_size}, shift_size={self.shift_size}, mlp_ratio={self.mlp_ratio}")
+
+    def custom_init_weights(self):
+        """The head transforms start as truncated normals with zero bias (:350-372)."""
+        for lst in (self.proj_l, self.proj_w):
+            for m in (lst or ()):
+                _trunc_normal(m.weight)
+                nn.init.constant_(m.bias, 0)
+
+
+class PatchMerging(nn.Module):
+    """:399-445: 2 x 2 neighbours concatenated (order (0,0), (1,0), (0,1), (1,1)), LayerNorm, 4C -> 2C without bias."""
+
+    def __init__(self, input_resolution, dim, norm_layer=nn.LayerNorm):
+        super().__init__()
+        self.input_resolution = input_resolution
+        self.dim = dim
+        self.reduction = nn.Linear(4 * dim, 2 * dim, bias=False)
+        self.norm = norm_layer(4 * dim)
+
+    def forward(self, x):
+        H, W = self.input_resolution
+        B, L, C = x.shape
+        assert L == H * W, "input feature has wrong size"
+        assert H % 2 == 0 and W % 2 == 0, f"x size ({H}*{W}) are not even."
+        x = x.view(B, H, W, C)
+        x = torch.cat([x[:, 0::2, 0::2], x[:, 1::2, 0::2], x[:, 0::2, 1::2], x[:, 1::2, 1::2]], -1)
+        return self.reduction(self.norm(x.view(B, -1, 4 * C)))
+
+    def extra_repr(self):
+        return f"input_resolution={self.input_resolution}, dim={self.dim}"
+
+
+class BasicLayer(nn.Module):
+    """:448-534: `separate_layer_num` blocks, each shared depth // separate_layer_num times."""
+
+    def __init__(self, dim, input_resolution, depth, num_heads, window_size, mlp_ratio=4., qkv_bias=True, qk_scale=None, drop=0.,
+                 attn_drop=0., drop_path=(0.,), norm_layer=nn.LayerNorm, downsample=None, use_checkpoint=False,
+                 is_sep_layernorm=False, is_transform_FFN=False, is_transform_heads=False, separate_layer_num=1):
+        super().__init__()
+        assert isinstance(drop_path, list)
+        self.dim = dim
+        self.input_resolution = input_resolution
+        self.depth = depth
+        self.use_checkpoint = use_checkpoint
+        self.share_times = depth // separate_layer_num
+        self.separate_layer_num = separate_layer_num
+        self.blocks = nn.ModuleList([
+            SwinTransformerBlock(dim=dim, input_resolution=input_resolution, num_heads=num_heads, window_size=window_size,
+                                 shift_size=window_size // 2, mlp_ratio=mlp_ratio, qkv_bias=qkv_bias, qk_scale=qk_scale, drop=drop,
+                                 attn_drop=attn_drop,
+                                 drop_path=drop_path[i * self.share_times:min((i + 1) * self.share_times, depth)],
+                                 norm_layer=norm_layer, is_init_window_shift=(i * self.share_times) % 2 == 1,
+                                 is_sep_layernorm=is_sep_layernorm, is_transform_FFN=is_transform_FFN,
+                                 is_transform_heads=is_transform_heads)
+            for i in range(separate_layer_num)])
+        self.downsample = downsample(input_resolution, dim=dim, norm_layer=norm_layer) if downsample is not None else None
+
+    def forward(self, x):
+        for blk in self.blocks:
+            if self.use_checkpoint:
+                from torch.utils import checkpoint
+                x = checkpoint.checkpoint(blk, x)
+            else:
+                x = blk(x)
+        return self.downsample(x) if self.downsample is not None else x
+
+    def extra_repr(self):
+        return f"dim={self.dim}, input_resolution={self.input_resolution}, depth={self.depth}"
+
+
+class PatchEmbed(nn.Module):
+    """:537-582."""
+
+    def __init__(self, img_size=224, patch_size=4, in_chans=3, embed_dim=96, norm_layer=None):
+        super().__init__()
+        self.img_size = _pair(img_size)
+        self.patch_size = _pair(patch_size)
+        self.patches_resolution = [self.img_size[0] // self.patch_size[0], self.img_size[1] // self.patch_size[1]]
+        self.num_patches = self.patches_resolution[0] * self.patches_resolution[1]
+        self.in_chans = in_chans
+        self.embed_dim = embed_dim
+        self.proj = nn.Conv2d(in_chans, embed_dim, kernel_size=self.patch_size, stride=self.patch_size)
+        self.norm = norm_layer(embed_dim) if norm_layer is not None else None
+
+    def forward(self, x):
+        B, C, H, W = x.shape
+        assert (H, W) == self.img_size, f"Input image size ({H}*{W}) doesn't match model ({self.img_size[0]}*{self.img_size[1]})."
+        x = self.proj(x).flatten(2).transpose(1, 2)
+        return self.norm(x) if self.norm is not None else x
+
+
+class SwinTransformerMiniViT(nn.Module):
+    """:585-732."""
+
+    def __init__(self, img_size=224, patch_size=4, in_chans=3, num_classes=1000, embed_dim=96, depths=(2, 2, 6, 2),
+                 num_heads=(3, 6, 12, 24), window_size=7, mlp_ratio=4., qkv_bias=True, qk_scale=None, drop_rate=0.,
+                 attn_drop_rate=0., drop_path_rate=0.1, norm_layer=nn.LayerNorm, ape=False, patch_norm=True, use_checkpoint=False,
+                 is_sep_layernorm=False, is_transform_FFN=False, is_transform_heads=False, separate_layer_num_list=(1, 1, 2, 1),
+                 **kwargs):
+        super().__init__()
+        self.num_classes = num_classes
+        self.num_layers = len(depths)
+        self.embed_dim = embed_dim
+        self.ape = ape
+        self.patch_norm = patch_norm
+        self.num_features = int(embed_dim * 2 ** (self.num_layers - 1))
+        self.mlp_ratio = mlp_ratio
+        self.is_sep_layernorm = is_sep_layernorm
+        self.is_transform_FFN = is_transform_FFN
+        self.is_transform_heads = is_transform_heads
+        self.separate_layer_num_list = separate_layer_num_list
+        self.patch_embed = PatchEmbed(img_size=img_size, patch_size=patch_size, in_chans=in_chans, embed_dim=embed_dim,
+                                      norm_layer=norm_layer if patch_norm else None)
+        res = self.patches_resolution = self.patch_embed.patches_resolution
+        if ape:
+            self.absolute_pos_embed = nn.Parameter(torch.zeros(1, self.patch_embed.num_patches, embed_dim))
+            _trunc_normal(self.absolute_pos_embed)
+        self.pos_drop = nn.Dropout(p=drop_rate)
+        dpr = [v.item() for v in torch.linspace(0, drop_path_rate, sum(depths))]
+        self.layers = nn.ModuleList()
+        for i in range(self.num_layers):
+            self.layers.append(BasicLayer(
+                dim=int(embed_dim * 2 ** i), input_resolution=(res[0] // 2 ** i, res[1] // 2 ** i), depth=depths[i],
+                num_heads=num_heads[i], window_size=window_size, mlp_ratio=mlp_ratio, qkv_bias=qkv_bias, qk_scale=qk_scale,
+                drop=drop_rate, attn_drop=attn_drop_rate, drop_path=dpr[sum(depths[:i]):sum(depths[:i + 1])], norm_layer=norm_layer,
+                downsample=PatchMerging if i < self.num_layers - 1 else None, use_checkpoint=use_checkpoint,
+                is_sep_layernorm=is_sep_layernorm, is_transform_FFN=is_transform_FFN, is_transform_heads=is_transform_heads,
+                separate_layer_num=separate_layer_num_list[i]))
+        self.norm = norm_layer(self.num_features)
+        self.avgpool = nn.AdaptiveAvgPool1d(1)
+        self.head = nn.Linear(self.num_features, num_classes) if num_classes > 0 else nn.Identity()
+        self.apply(self._init_weights)
+        for m in self.modules():
+            if isinstance(m, SwinTransformerBlock):
+                m.custom_init_weights()
+
+    @staticmethod
+    def _init_weights(m):
+        if isinstance(m, nn.Linear):
+            _trunc_normal(m.weight)
+            if m.bias is not None:
+                nn.init.constant_(m.bias, 0)
+        elif isinstance(m, nn.LayerNorm):
+            nn.init.constant_(m.bias, 0)
+            nn.init.constant_(m.weight, 1.0)
+
+    @torch.jit.ignore
+    def no_weight_decay(self):
+        return {'absolute_pos_embed'}
+
+    @torch.jit.ignore
+    def no_weight_decay_keywords(self):
+        return {'relative_position_bias_table'}
+
+    def forward_features(self, x):
+        x = self.patch_embed(x)
+        if self.ape:
+            x = x + self.absolute_pos_embed
+        x = self.pos_drop(x)
+        for layer in self.layers:
+            x = layer(x)
+        x = self.norm(x)
+        return torch.flatten(self.avgpool(x.transpose(1, 2)), 1)
+
+    def forward(self, x):
+        return self.head(self.forward_features(x))
+
+
+# the published Mini-Swin recipes (Mini-Swin/configs/swin_{tiny,small,base}_patch4_window7_224_minivit_sharenum*.yaml)
+_SWIN = dict(tiny=dict(embed_dim=96, depths=[2, 2, 6, 2], num_heads=[3, 6, 12, 24], separate_layer_num_list=[1, 1, 1, 1],
+                       drop_path_rate=0.0),
+             small=dict(embed_dim=96, depths=[2, 2, 18, 2], num_heads=[3, 6, 12, 24], separate_layer_num_list=[1, 1, 9, 1],
+                        drop_path_rate=0.1),
+             base=dict(embed_dim=128, depths=[2, 2, 18, 2], num_heads=[4, 8, 16, 32], separate_layer_num_list=[1, 1, 9, 1],
+                       drop_path_rate=0.2))
+
+
+def mini_swin(size='tiny', img_size=224, **kwargs):
+    """Mini-Swin-{T,S,B} at 224 with window 7: every stage's blocks shared (tiny) or shared in pairs in stage 3 (small,
+    base), per-repeat LayerNorms, head transforms and local convolutions on."""
+    kw = dict(img_size=img_size, patch_size=4, window_size=7, mlp_ratio=4., qkv_bias=True, is_sep_layernorm=True,
+              is_transform_FFN=True, is_transform_heads=True)
+    kw.update(_SWIN[size])
+    kw.update(kwargs)
+    return SwinTransformerMiniViT(**kw)

@@ -350,6 +350,57 @@ int cream_mini_attn_fwd(const cream_mini_attn_desc* d, void* stream);
 /* dq, dk, dv, the dlk rows and the partials of d wl / d ww from dout and lse.  2 + ceil(H / 4) launches. */
 int cream_mini_attn_bwd(const cream_mini_attn_desc* d, void* stream);
 
+/* ---- fused (shifted-)window attention of Swin / Mini-Swin ---------------------------------------------------------
+ * WindowAttention.forward between the qkv and proj linears, with the cyclic shift, window partition and reverse of
+ * SwinTransformerBlock.forward_feature in the addressing (MiniViT/Mini-Swin/models/swin_transformer_minivit.py:109-147,
+ * :284-323) — see csrc/window_attn.hip for the formulas:
+ *     S_h = (s q_h) k_h^T + table[rel(i,j), h],  S'_o = sum_h wl[o,h] S_h + bl[o] (+ mask in {0, -100}),
+ *     P_o = softmax(S'_o),  P'_o = sum_h ww[o,h] P_h + bw[o],  O_o = P'_o v_o.
+ * q, k, v are the projection of the UNSHIFTED, UNPARTITIONED (Hs x Ws) map, token n = y * Ws + x; out has the same token
+ * order.  Window (wy, wx), local (iy, ix) is token ((wy w + iy + shift) mod Hs, (wx w + ix + shift) mod Ws).  mask_shift
+ * m > 0 adds -100 between tokens of different regions of the shifted frame (three slices per axis: [0, Hs - w),
+ * [Hs - w, Hs - m), [Hs - m, Hs)); the reference applies a block's mask whether or not the repeat rolls the map, hence
+ * two arguments.  bf16 operands, fp32 accumulation; head_dim 32, square windows with w * w <= 64, Hs and Ws multiples of
+ * w, shift < w, mask_shift < w; wl, bl, ww, bw all NULL (no head transforms, 1 <= H <= 32) or all given (1 <= H <= 16).
+ * Anything else returns CREAM_ERR_BAD_ARG before any HIP call; B == 0 is a no-op.  Nothing of size N^2 per window is
+ * written; no global atomics: the backward's parameter gradients come as one partial per workgroup of its persistent
+ * grid, (part_blocks, part_size) fp32 = [d table ((2w-1)^2, H) | d wl (H, H) | d ww (H, H) | d bl (H) | d bw (H)] (the
+ * last four only with head transforms), which the caller sums over the first axis. */
+typedef struct cream_window_attn_desc {
+    const void *q, *k, *v;          /* bf16; element (b, n, h, :) at ptr[b*sb + n*sn + h*sh]                 */
+    int64_t sb, sn, sh;
+    void* out;                      /* (B, Hs*Ws, H, 32) bf16 (fwd only)                                   */
+    float* lse;                     /* (B * nW, H, 64): log-sum-exp of the mixed, masked logits (fwd: out, bwd: in) */
+    const float* table;             /* ((2w-1)^2, H) fp32                                                  */
+    const float *wl, *bl, *ww, *bw; /* (H, H) [out][in] and (H) fp32, or all NULL                          */
+    int32_t B, H, Hs, Ws, w, shift, mask_shift, head_dim;
+    float scale;
+    int32_t part_blocks;            /* bwd: cream_window_attn_blocks(d), the first axis of `part`           */
+    /* backward only */
+    const void* dout;               /* (B, Hs*Ws, H, 32) bf16                                              */
+    void *dq, *dk, *dv;             /* bf16; element (b, n, h, :) at ptr[b*dsb + n*dsn + h*dsh]             */
+    int64_t dsb, dsn, dsh;
+    float* delta;                   /* (B * nW, H, 64) scratch                                             */
+    float* part;                    /* (part_blocks, cream_window_attn_part_size(H, w, mixed)) fp32 out     */
+} cream_window_attn_desc;
+
+/* The argument check of the calls below alone (backward != 0: of cream_window_attn_bwd, except part_blocks' value):
+ * CREAM_OK or the error code.  Pure host arithmetic. */
+int cream_window_attn_check(const cream_window_attn_desc* d, int backward);
+
+/* Floats per workgroup partial, or CREAM_ERR_BAD_ARG.  Pure host arithmetic. */
+int cream_window_attn_part_size(int H, int w, int mixed);
+
+/* Workgroups of the persistent grids for this descriptor's shape (B, H, Hs, Ws, w, head transforms or not; from
+ * cream_cu_count(); the data pointers are not looked at), 0 when B == 0, or an error code. */
+int cream_window_attn_blocks(const cream_window_attn_desc* d);
+
+/* out and lse from q, k, v.  One launch. */
+int cream_window_attn_fwd(const cream_window_attn_desc* d, void* stream);
+
+/* dq, dk, dv and the partials of the parameter gradients from dout and lse.  Two launches. */
+int cream_window_attn_bwd(const cream_window_attn_desc* d, void* stream);
+
 /* ---- fused iRPE attention, generalised: 32- or 64-wide heads, up to 128 buckets, key padding mask -------------
  * The same operator as cream_irpe_attn_fwd / _bwd (same formulas, launches and conventions; csrc/irpe_attn_x.hip),
  * for the callers those entry points refuse: DETR-with-iRPE's encoder self-attention (d_model 256 / 8 heads = 32,
