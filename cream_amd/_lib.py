@@ -61,6 +61,13 @@ SIGNATURES = {
     "cream_window_attn_blocks": (_i, [_vp]),
     "cream_window_attn_fwd": (_i, [_vp, _vp]),
     "cream_window_attn_bwd": (_i, [_vp, _vp]),
+    "cream_relation_loss_check": (_i, [_vp]),
+    "cream_relation_loss_blocks": (_i, [_vp]),
+    "cream_relation_loss": (_i, [_vp, _vp]),
+    "cream_hidden_relation_check": (_i, [_vp]),
+    "cream_hidden_relation_padded": (_i, [_i]),
+    "cream_hidden_relation_parts": (_i, [_i, _i]),
+    "cream_hidden_relation_loss": (_i, [_vp, _vp]),
     "cream_attn_rpe2d_padded_len": (_i, [_i]),
     "cream_attn_rpe2d_dtab_parts": (_i, [_i, _i]),
     "cream_attn_rpe2d_bwd_mode": (_i, [_i]),
@@ -226,6 +233,25 @@ class WindowAttnDesc(ctypes.Structure):
                 [("scale", _f), ("part_blocks", _c.c_int32)] +
                 [(n, _vp) for n in ("dout", "dq", "dk", "dv")] + [(n, _i64) for n in ("dsb", "dsn", "dsh")] +
                 [(n, _vp) for n in ("delta", "part")])
+
+
+class RelationSide(ctypes.Structure):
+    """struct cream_relation_side of include/cream_amd.h."""
+    _fields_ = ([(n, _vp) for n in ("q", "k", "v")] + [(n, _i64) for n in ("sb", "sn")] +
+                [(n, _c.c_int32) for n in ("B", "C", "Hs", "Ws", "w", "shift")])
+
+
+class RelationDesc(ctypes.Structure):
+    """struct cream_relation_desc of include/cream_amd.h."""
+    _fields_ = ([("s", RelationSide), ("t", RelationSide), ("Ar", _c.c_int32), ("want_grad", _c.c_int32), ("coef", _f),
+                 ("part_blocks", _c.c_int32)] + [(n, _vp) for n in ("part", "dq", "dk", "dv")] + [(n, _i64) for n in ("dsb", "dsn")])
+
+
+class HiddenRelationDesc(ctypes.Structure):
+    """struct cream_hidden_relation_desc of include/cream_amd.h."""
+    _fields_ = ([(n, _vp) for n in ("s", "t")] +
+                [(n, _c.c_int32) for n in ("s_dtype", "t_dtype", "B", "L", "Cs", "Ct", "want_grad")] + [("coef", _f)] +
+                [(n, _vp) for n in ("sn", "tn", "s_rinv", "t_rinv", "g", "part", "ds")])
 
 
 class ParamJob(ctypes.Structure):

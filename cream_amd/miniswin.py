@@ -21,11 +21,17 @@ Two paths through `SwinTransformerBlock.forward_feature`:
   * composed — everything else (fp32, CPU, window 12, active attention dropout, more than 16 mixed heads): the
     reference's arithmetic step by step.
 The depthwise local convolution, patch merging and patch embedding stay with the framework.
+
+The distilling models (`SwinTransformerMiniViTDistill`, mirror of swin_transformer_minivit_distill.py:447-621, and the plain
+Swin teacher `SwinTransformerDistill`, mirror of swin_transformer_distill.py) return, per layer id listed, a TAP of the
+attention's q, k, v — a `minivit_distill.QkvTap` on the fused path, the reference's tuple of windowed views on the composed one
+— and the block's output; cream_amd.minivit_distill turns them into the relation losses.
 """
 import torch
 import torch.nn as nn
 
 from . import window_attn
+from .minivit_distill import QkvTap
 from .rpe_attention import DropPath
 
 
@@ -207,6 +213,7 @@ class SwinTransformerBlock(nn.Module):
                 self.local_conv_list.append(nn.Conv2d(dim, dim, 7, 1, 3, groups=dim, bias=qkv_bias))
         else:
             self.local_conv_list = None
+        self._taps = None                                    # forward_taps: the list the attention's q, k, v go to
 
     def forward_feature(self, x, is_shift=False, layer_index=0):
         H, W = self.input_resolution
@@ -220,12 +227,16 @@ class SwinTransformerBlock(nn.Module):
         w = self.window_size
         qkv = self.attn.qkv(x)                               # per token: commutes with the roll and the partition
         if self.attn.usable(qkv, w, proj_l, proj_w):
+            if self._taps is not None:
+                self._taps.append(QkvTap(qkv, (H, W, w, shift)))
             x = self.attn.forward_map(qkv, (H, W, w, shift, self.shift_size), proj_l, proj_w)
         else:
             qkv = qkv.view(B, H, W, 3 * C)
             if shift > 0:
                 qkv = torch.roll(qkv, shifts=(-shift, -shift), dims=(1, 2))
             windows = window_partition(qkv, w).reshape(-1, w * w, 3 * C)
+            if self._taps is not None:                       # the reference's tuple: (B * nW, N, C) views (:71, :100)
+                self._taps.append(windows.view(-1, w * w, 3, C).unbind(2))
             x = self.attn.attend(windows, mask=self.attn_mask, proj_l=proj_l, proj_w=proj_w)      # the mask in every repeat (:312)
             x = window_reverse(x.view(-1, w, w, C), w, H, W)
             if shift > 0:
@@ -246,6 +257,20 @@ class SwinTransformerBlock(nn.Module):
             x = self.forward_feature(x, shift, index)
             shift = not shift
         return x
+
+    def forward_taps(self, x):
+        """`forward` of the distilling block (swin_transformer_minivit_distill.py:291-300): -> (x, one tap of q, k, v per
+        repeat, the output of every repeat)."""
+        self._taps, hidden = [], []
+        try:
+            shift = self.is_init_window_shift
+            for index in range(self.share_num):
+                x = self.forward_feature(x, shift, index)
+                hidden.append(x)
+                shift = not shift
+            return x, self._taps, hidden
+        finally:
+            self._taps = None
 
     def extra_repr(self):
         return (f"dim={self.dim}, input_resolution={self.input_resolution}, num_heads={self.num_heads}, "
@@ -316,8 +341,41 @@ class BasicLayer(nn.Module):
                 x = blk(x)
         return self.downsample(x) if self.downsample is not None else x
 
+    def forward_taps(self, x):
+        """The distilling layer (swin_transformer_minivit_distill.py:422-434): the hidden states are the blocks' outputs before
+        patch merging."""
+        taps, hidden = [], []
+        for blk in self.blocks:
+            x, t, h = blk.forward_taps(x)
+            taps += t
+            hidden += h
+        return (self.downsample(x) if self.downsample is not None else x), taps, hidden
+
     def extra_repr(self):
         return f"dim={self.dim}, input_resolution={self.input_resolution}, depth={self.depth}"
+
+
+class SwinBasicLayer(BasicLayer):
+    """A stage of the plain Swin Transformer (swin_transformer_distill.py:235-300): `depth` unshared blocks, the odd ones
+    shifted, the even ones without shift AND without mask.  Takes BasicLayer's arguments; the MiniViT ones are ignored."""
+
+    def __init__(self, dim, input_resolution, depth, num_heads, window_size, mlp_ratio=4., qkv_bias=True, qk_scale=None, drop=0.,
+                 attn_drop=0., drop_path=(0.,), norm_layer=nn.LayerNorm, downsample=None, use_checkpoint=False, **minivit):
+        nn.Module.__init__(self)
+        self.dim = dim
+        self.input_resolution = input_resolution
+        self.depth = depth
+        self.use_checkpoint = use_checkpoint
+        self.share_times = 1
+        self.separate_layer_num = depth
+        self.blocks = nn.ModuleList([
+            SwinTransformerBlock(dim=dim, input_resolution=input_resolution, num_heads=num_heads, window_size=window_size,
+                                 shift_size=0 if i % 2 == 0 else window_size // 2, mlp_ratio=mlp_ratio, qkv_bias=qkv_bias,
+                                 qk_scale=qk_scale, drop=drop, attn_drop=attn_drop,
+                                 drop_path=[drop_path[i] if isinstance(drop_path, (list, tuple)) else drop_path],
+                                 norm_layer=norm_layer, is_init_window_shift=i % 2 == 1)
+            for i in range(depth)])
+        self.downsample = downsample(input_resolution, dim=dim, norm_layer=norm_layer) if downsample is not None else None
 
 
 class PatchEmbed(nn.Module):
@@ -343,6 +401,7 @@ class PatchEmbed(nn.Module):
 
 class SwinTransformerMiniViT(nn.Module):
     """:585-732."""
+    layer_class = BasicLayer
 
     def __init__(self, img_size=224, patch_size=4, in_chans=3, num_classes=1000, embed_dim=96, depths=(2, 2, 6, 2),
                  num_heads=(3, 6, 12, 24), window_size=7, mlp_ratio=4., qkv_bias=True, qk_scale=None, drop_rate=0.,
@@ -371,7 +430,7 @@ class SwinTransformerMiniViT(nn.Module):
         dpr = [v.item() for v in torch.linspace(0, drop_path_rate, sum(depths))]
         self.layers = nn.ModuleList()
         for i in range(self.num_layers):
-            self.layers.append(BasicLayer(
+            self.layers.append(self.layer_class(
                 dim=int(embed_dim * 2 ** i), input_resolution=(res[0] // 2 ** i, res[1] // 2 ** i), depth=depths[i],
                 num_heads=num_heads[i], window_size=window_size, mlp_ratio=mlp_ratio, qkv_bias=qkv_bias, qk_scale=qk_scale,
                 drop=drop_rate, attn_drop=attn_drop_rate, drop_path=dpr[sum(depths[:i]):sum(depths[:i + 1])], norm_layer=norm_layer,
@@ -416,6 +475,73 @@ class SwinTransformerMiniViT(nn.Module):
 
     def forward(self, x):
         return self.head(self.forward_features(x))
+
+
+class SwinTransformerMiniViTDistill(SwinTransformerMiniViT):
+    """swin_transformer_minivit_distill.py:447-621: SwinTransformerMiniViT that also returns, for the layer ids listed (counted
+    over the repeats of all stages), a tap of the attention's q, k, v and the hidden state; a student carries one
+    `fit_dense_C.{i}` = nn.Linear(embed_dim 2^i, fit_size_C 2^i) per stage for the plain hidden loss."""
+
+    def __init__(self, *args, is_student=False, fit_size_C=128, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.is_student = is_student
+        self.fit_size_C = fit_size_C
+        self.fit_dense_C = nn.ModuleList()
+        if is_student:
+            for i in range(self.num_layers):
+                self.fit_dense_C.append(nn.Linear(int(self.embed_dim * 2 ** i), int(fit_size_C * 2 ** i)))
+        self.fit_dense_C.apply(self._init_weights)
+
+    def forward_features(self, x, layer_id_list=(), is_hidden_org=True):
+        """:580-604."""
+        x = self.patch_embed(x)
+        if self.ape:
+            x = x + self.absolute_pos_embed
+        x = self.pos_drop(x)
+        layer_id = 0
+        taps_out, hidden_out = [], []
+        for i, layer in enumerate(self.layers):
+            x, taps, hidden = layer.forward_taps(x)
+            for index in range(len(taps)):
+                if index + layer_id in layer_id_list:
+                    taps_out.append(taps[index])
+                    fit = self.is_student and not is_hidden_org
+                    hidden_out.append(self.fit_dense_C[i](hidden[index]) if fit else hidden[index])
+            layer_id += len(taps)
+        x = self.norm(x)
+        return torch.flatten(self.avgpool(x.transpose(1, 2)), 1), taps_out, hidden_out
+
+    def forward(self, x, layer_id_list=(), is_attn_loss=False, is_hidden_loss=False, is_hidden_org=True):
+        """:606-621: logits | (logits, taps) | (logits, hidden) | (logits, taps, hidden)."""
+        x, taps, hidden = self.forward_features(x, layer_id_list, is_hidden_org=is_hidden_org)
+        x = self.head(x)
+        if is_attn_loss and is_hidden_loss:
+            return x, taps, hidden
+        if is_attn_loss:
+            return x, taps
+        if is_hidden_loss:
+            return x, hidden
+        return x
+
+
+class SwinTransformerDistill(SwinTransformerMiniViTDistill):
+    """swin_transformer_distill.py:309-464: the plain Swin Transformer (the teacher) with the same taps, under the plain Swin's
+    parameter names (`layers.{i}.blocks.{j}.norm1`, `.attn.*`, `.norm2`, `.mlp.*`; `attn_mask` on the shifted blocks only), so
+    that a Swin checkpoint loads."""
+    layer_class = SwinBasicLayer
+
+    def __init__(self, img_size=224, patch_size=4, in_chans=3, num_classes=1000, embed_dim=96, depths=(2, 2, 6, 2),
+                 num_heads=(3, 6, 12, 24), window_size=7, mlp_ratio=4., qkv_bias=True, qk_scale=None, drop_rate=0.,
+                 attn_drop_rate=0., drop_path_rate=0.1, norm_layer=nn.LayerNorm, ape=False, patch_norm=True, use_checkpoint=False,
+                 is_student=False, fit_size_C=128, **kwargs):
+        super().__init__(img_size=img_size, patch_size=patch_size, in_chans=in_chans, num_classes=num_classes, embed_dim=embed_dim,
+                         depths=depths, num_heads=num_heads, window_size=window_size, mlp_ratio=mlp_ratio, qkv_bias=qkv_bias,
+                         qk_scale=qk_scale, drop_rate=drop_rate, attn_drop_rate=attn_drop_rate, drop_path_rate=drop_path_rate,
+                         norm_layer=norm_layer, ape=ape, patch_norm=patch_norm, use_checkpoint=use_checkpoint,
+                         separate_layer_num_list=list(depths), is_student=is_student, fit_size_C=fit_size_C)
+
+    def forward(self, x, layer_id_list=(), is_attn_loss=False, is_hidden_loss=False, is_hidden_org=False):
+        return super().forward(x, layer_id_list, is_attn_loss, is_hidden_loss, is_hidden_org)
 
 
 # the published Mini-Swin recipes (Mini-Swin/configs/swin_{tiny,small,base}_patch4_window7_224_minivit_sharenum*.yaml)

@@ -401,6 +401,63 @@ int cream_window_attn_fwd(const cream_window_attn_desc* d, void* stream);
 /* dq, dk, dv and the partials of the parameter gradients from dout and lse.  Two launches. */
 int cream_window_attn_bwd(const cream_window_attn_desc* d, void* stream);
 
+/* ---- the relation losses of the Mini-Swin distillation step (csrc/distill_loss.hip) -------------------------------
+ * cal_relation_loss and cal_hidden_relation_loss of MiniViT/Mini-Swin/main.py:39-57 and :66-77, each with the gradient
+ * with respect to the student in the same call.  No atomics: one fp32 partial of the (already scaled) loss per workgroup,
+ * which the caller sums; every gradient element is written once.  Nothing of size N^2 per window or L^2 per image is
+ * written.
+ *
+ * Relation loss: per window of w * w <= 64 tokens, per channel group of Ar and per ordered pair (i, j) of {q, k, v}
+ *     A_s = X_i X_j^T / sqrt(Cs / Ar),  A_t = Y_i Y_j^T / sqrt(Ct / Ar),  loss += coef * sum_rows -softmax(A_t) . log_softmax(A_s)
+ *     G_ij = coef (softmax(A_s) - softmax(A_t)):  dX_i += G_ij X_j / sqrt(Cs / Ar),  dX_j += G_ij^T X_i / sqrt(Cs / Ar).
+ * A side is B maps of Hs x Ws tokens (token n = y * Ws + x, channel stride 1), partitioned into w x w windows after a cyclic
+ * shift as in cream_window_attn_desc; windows that are already partitioned are B * nW maps of w x w.  Both sides have the
+ * same w and the same number of windows, C / Ar is a multiple of 32 on both; everything else may differ. */
+typedef struct cream_relation_side {
+    const void *q, *k, *v;          /* bf16; element (b, n, c) at ptr[b*sb + n*sn + c]                      */
+    int64_t sb, sn;
+    int32_t B, C, Hs, Ws, w, shift;
+} cream_relation_side;
+
+typedef struct cream_relation_desc {
+    cream_relation_side s, t;       /* student, teacher                                                    */
+    int32_t Ar, want_grad;
+    float coef;                     /* 1 / (rows * 9 * layers), rows = windows * Ar * w * w                */
+    int32_t part_blocks;            /* cream_relation_loss_blocks(d), the length of `part`                 */
+    float* part;
+    void *dq, *dk, *dv;             /* want_grad: bf16; element (b, n, c) at ptr[b*dsb + n*dsn + c]         */
+    int64_t dsb, dsn;
+} cream_relation_desc;
+
+/* The argument check of cream_relation_loss alone (except part_blocks' value).  Pure host arithmetic. */
+int cream_relation_loss_check(const cream_relation_desc* d);
+
+/* Workgroups of the persistent grid for this descriptor's shapes and want_grad (from cream_cu_count(); the data pointers
+ * are not looked at), 0 for an empty batch, or an error code. */
+int cream_relation_loss_blocks(const cream_relation_desc* d);
+
+/* part, and with want_grad dq, dk, dv.  One launch. */
+int cream_relation_loss(const cream_relation_desc* d, void* stream);
+
+/* Hidden relation loss of hidden states s (B, L, Cs) and t (B, L, Ct), contiguous, fp32 or bf16 each:
+ *     S^ = s / max(|s|, 1e-12) per row (norms in fp32), T^ likewise,  D = S^ S^^T - T^ T^^T,  loss = coef * sum D^2,
+ *     ds = (g - S^ (S^ . g)) / max(|s|, 1e-12)  with  g_i = 4 coef sum_j D_ij S^_j,   in s's dtype.
+ * Scratch: sn (B, L, P(Cs)) and tn (B, L, P(Ct)) bf16 with P = cream_hidden_relation_padded, s_rinv and t_rinv (B, L) fp32,
+ * with want_grad g (B, L, P(Cs)) fp32; part: cream_hidden_relation_parts(B, L) floats.  Up to four launches. */
+typedef struct cream_hidden_relation_desc {
+    const void *s, *t;
+    int32_t s_dtype, t_dtype, B, L, Cs, Ct, want_grad;
+    float coef;                     /* 49 / (B * L * L * layers)                                           */
+    void *sn, *tn;
+    float *s_rinv, *t_rinv, *g, *part;
+    void* ds;                       /* want_grad: (B, L, Cs) in s_dtype                                    */
+} cream_hidden_relation_desc;
+
+int cream_hidden_relation_check(const cream_hidden_relation_desc* d);
+int cream_hidden_relation_padded(int C);
+int cream_hidden_relation_parts(int B, int L);
+int cream_hidden_relation_loss(const cream_hidden_relation_desc* d, void* stream);
+
 /* ---- fused iRPE attention, generalised: 32- or 64-wide heads, up to 128 buckets, key padding mask -------------
  * The same operator as cream_irpe_attn_fwd / _bwd (same formulas, launches and conventions; csrc/irpe_attn_x.hip),
  * for the callers those entry points refuse: DETR-with-iRPE's encoder self-attention (d_model 256 / 8 heads = 32,
