@@ -271,6 +271,24 @@ class BlockGrads(ctypes.Structure):
 _lib = None
 
 
+# the attention descriptors that take the packed qkv projection (IrpeAttnDesc, MiniAttnDesc, WindowAttnDesc) name its parts alike
+def _packed_parts(t):
+    """Packed (B, L, 3, H, D) tensor -> (pointers of its three parts, (batch, token, head) strides in elements)."""
+    sb, sn, s3, sh, _ = t.stride()
+    base, step = t.data_ptr(), s3 * t.element_size()
+    return (base, base + step, base + 2 * step), (sb, sn, sh)
+
+
+def set_packed_qkv(d, qkv):
+    """Fills q / k / v and sb / sn / sh of a descriptor from the packed (B, L, 3, H, D) projection."""
+    (d.q, d.k, d.v), (d.sb, d.sn, d.sh) = _packed_parts(qkv)
+
+
+def set_packed_dqkv(d, dqkv):
+    """Fills dq / dk / dv and dsb / dsn / dsh of a descriptor from the packed (B, L, 3, H, D) gradient."""
+    (d.dq, d.dk, d.dv), (d.dsb, d.dsn, d.dsh) = _packed_parts(dqkv)
+
+
 def load():
     """Load the library once and bind every declared entry point."""
     global _lib

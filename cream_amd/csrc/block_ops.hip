@@ -22,17 +22,12 @@
 #include <stdlib.h>
 
 #include "attn_common.hpp"
+#include "lane_ops.hpp"
 #include "cream_amd.h"
 #include "launch_ev.hpp"
 
 namespace {
 using namespace cream;
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 __device__ __forceinline__ float gelu_f(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752f)); }
 __device__ __forceinline__ float gelu_grad_f(float x) {

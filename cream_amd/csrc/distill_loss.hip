@@ -30,14 +30,12 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "attn_common.hpp"
+#include "attn_lane.hpp"
 #include "cream_amd.h"
 #include "cu_budget.hpp"
 
 namespace {
 using namespace cream;
-using TT = Tr<hip_bfloat16>;
-using F = TT::frag;
 
 constexpr int GP = 64;                 // pitch (bf16) of the G matrices: 64 x 64, read once per chunk and unit
 constexpr int XP = 72;                 // pitch (bf16) of the transposed [32 channels][64 tokens] chunks
@@ -293,11 +291,6 @@ constexpr int HCH = 128;               // channels of g per workgroup of the til
 __device__ __forceinline__ float load_elem(const void* p, int64_t i, int bf16) {
     return bf16 ? bf2f(reinterpret_cast<const short*>(p)[i]) : reinterpret_cast<const float*>(p)[i];
 }
-__device__ __forceinline__ float wave_sum64(float v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 // one wave per row: unit row as bf16 (zero-padded to Cp channels) and 1 / max(|x|, eps)
 __global__ __launch_bounds__(256) void hidden_rows_kernel(const void* x, int bf16, int64_t rows, int C, int Cp, short* xn, float* rinv) {
@@ -309,7 +302,7 @@ __global__ __launch_bounds__(256) void hidden_rows_kernel(const void* x, int bf1
         const float v = load_elem(x, row * C + c, bf16);
         ss += v * v;
     }
-    const float ri = 1.f / fmaxf(sqrtf(wave_sum64(ss)), NORM_EPS);
+    const float ri = 1.f / fmaxf(sqrtf(wave_sum(ss)), NORM_EPS);
     for (int c = lane; c < Cp; c += 64) xn[row * Cp + c] = c < C ? f2bf(load_elem(x, row * C + c, bf16) * ri) : (short)0;
     if (lane == 0) rinv[row] = ri;
 }
@@ -409,7 +402,7 @@ __global__ __launch_bounds__(256) void hidden_epilogue_kernel(const void* x, int
     const bool clamped = ri >= 1.f / NORM_EPS;
     float dot = 0.f;
     for (int c = lane; c < C; c += 64) dot += load_elem(x, row * C + c, bf16) * ri * gsum[row * Cp + c];
-    dot = clamped ? 0.f : wave_sum64(dot);
+    dot = clamped ? 0.f : wave_sum(dot);
     for (int c = lane; c < C; c += 64) {
         const float v = coef4 * (gsum[row * Cp + c] - load_elem(x, row * C + c, bf16) * ri * dot) * ri;
         if (bf16) reinterpret_cast<short*>(dx)[row * C + c] = f2bf(v);

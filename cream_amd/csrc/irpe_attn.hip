@@ -38,19 +38,20 @@
 // Launch A (lanes own queries): delta, dq, dLK rows; hands LK and G rows to launch B.  Launch B (lanes
 // own keys): dk, dv, dLQ rows.  The three table gradients are per-(b,h) 64 x 64 products over tokens
 // (`irpe_table_grad_kernel`), reduced over b (and h for shared tables) by the caller.  No global atomics.
+//
+// The lane-level pieces (ids_load / off2_of / add_bf16_at, scatter_add16, load_perm_tr, srow_frag, store_row, ...) are in
+// attn_lane.hpp, shared with irpe_attn_x.hip and mini_attn.hip; this file keeps the tiles, the LDS carve-ups and the loops.
 #include <hip/hip_runtime.h>
 #include <hip/hip_bfloat16.h>
 #include <stdint.h>
 
 #include <type_traits>
 
-#include "attn_common.hpp"
+#include "attn_lane.hpp"
 #include "cream_amd.h"
 
 namespace {
 using namespace cream;
-using TT = Tr<hip_bfloat16>;
-using F = TT::frag;
 
 constexpr float LOG2E = 1.4426950408889634f;
 constexpr int KP = 72;      // pitch (bf16) of row-major [32][64] tiles and of the [64][64] tables
@@ -116,22 +117,6 @@ struct Args {
 
 // (keep mask: mix32 / drop_key / drop_keep in attn_common.hpp)
 
-// consecutive logical workgroups (the blocks of one (b,h), which share the streamed side) on one XCD
-__device__ __forceinline__ int xcd_order(int bid, int n) {
-    if (n & 7) return bid;
-    return (bid & 7) * (n >> 3) + (bid >> 3);
-}
-
-__device__ __forceinline__ F scaled(const F x, float s) {
-    f32x8v y;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) y[e] = bf2f(x[e]) * s;
-    return __builtin_bit_cast(F, __builtin_convertvector(y, hwbf16x8));
-}
-__device__ __forceinline__ u32x4v scaled_raw(const u32x4v x, float s) {
-    return __builtin_bit_cast(u32x4v, scaled(__builtin_bit_cast(F, x), s));
-}
-
 // dst[c][r] = src[r][c] (src: nrow x ncol fp32, zero outside) as bf16 operand rows of pitch KP
 __device__ __forceinline__ void stage_table_T(short* dst, const float* src, int nrow, int ncol) {
     for (int i = threadIdx.x; i < 64 * 64; i += 256) {
@@ -174,61 +159,11 @@ template <int LBP> __device__ __forceinline__ void lrows_store(short* dst, const
     for (int i = 0; i < 4; ++i)
         if (LBP >= 64 || cc * 8 + 2 * i + 1 < LBP) d[i] = x[i];
 }
-// The 16 bucket ids of this lane's (own row, partners acc_row(r, g), r = 0..15) of streamed tile t: ONE 16-byte load from the
-// byte matrix straight into registers.  bucket_bytes_kernel stores every 32-byte group of a row in that order (lane group g = 0
-// first), so the two lanes of an own row read the two halves of one 32-byte piece and a wave reads 32 such pieces — the access
-// pattern the staged id tiles had (round 2-5: a (128 x 32)-byte tile per table, double-buffered in LDS, 27 KB with rpe on q, k
-// and v), without the LDS tile, its store and its four reads per lane.
-__device__ __forceinline__ u32x4v ids_load(const uint8_t* tab, int NP, int row, int t, int g) {
-    return *reinterpret_cast<const u32x4v*>(tab + (int64_t)min(row, NP - 1) * NP + t * 32 + g * 16);
-}
-// the bytes hold 2 * bucket id: the byte offset of the bucket in a bf16 lookup row
-__device__ __forceinline__ int off2_of(const u32x4v& w, int r) { return (w[r >> 2] >> (8 * (r & 3))) & 0xffu; }
-// acc += (bf16 at byte offset off2 of row): one v_dot2c_f32_bf16 with (x, 0) . (1, 1) instead of shift + add
-typedef __bf16 hwbf16x2v __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ float add_bf16_at(float acc, const short* row, int off2) {
-    const uint32_t x = *reinterpret_cast<const unsigned short*>(reinterpret_cast<const char*>(row) + off2);
-    return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(hwbf16x2v, x), __builtin_bit_cast(hwbf16x2v, 0x3F803F80u), acc, false);   // (1, 1): a literal — the inline constant 1.0 is not (1, 0) for packed bf16
-}
-
-// row[id_r] += val_r for the 16 (bucket id, value) pairs of this lane — without LDS float atomics
-// (ds_add_f32 retires a few lanes per clock: the kernels were 6x slower with it, profiles/r02_irpe_attention.md).
-// The two lanes that share a row (g = 0 / 1) take turns — the LDS operations of a wave execute in order, so
-// the second half adds onto the first half's sums — and each half goes 8 pairs at a time: 8 reads,
-// duplicates inside the group resolved in registers (the latest earlier match carries the running sum,
-// and the last write to an address is the complete one), 8 writes.
+// pairs per read-modify-write group of scatter_add16 (attn_lane.hpp, where the measurement behind the 4 is); a macro so that
+// tools/probe_irpe_variants.sh can build the other group sizes
 #ifndef IRPE_SCATTER_GROUP
-#define IRPE_SCATTER_GROUP 4      // pairs per read-modify-write group.  Same-call A/B at config 4 (tools/probe_irpe_variants.sh, two workgroups per
-#endif                            // CU): 16 / 8 / 4 / 2 -> forward v 413 / 313 / 274 / 274 us, backward k 1,042 / 930 / 870 / 870: with a second wave on
-                                  // the SIMD the extra LDS round trips are hidden and the compare / select pairs (G (G - 1) / 2 per group) are not
-__device__ __forceinline__ void scatter_add16(float* row, const u32x4v& w, const f32x16& val, int g) {
-    constexpr int G = IRPE_SCATTER_GROUP;
-#pragma unroll
-    for (int half = 0; half < 2; ++half) {
-        if (g == half) {
-#pragma unroll
-            for (int grp = 0; grp < 16 / G; ++grp) {
-                int id[G];
-                float sum[G];
-#pragma unroll
-                for (int v = 0; v < G; ++v) {
-                    id[v] = off2_of(w, grp * G + v);
-                    sum[v] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(row) + 2 * id[v]);
-                }
-#pragma unroll
-                for (int v = 0; v < G; ++v) {
-                    float base = sum[v];
-#pragma unroll
-                    for (int u = 0; u < v; ++u) base = (id[u] == id[v]) ? sum[u] : base;
-                    sum[v] = base + val[grp * G + v];
-                }
-#pragma unroll
-                for (int v = 0; v < G; ++v) *reinterpret_cast<float*>(reinterpret_cast<char*>(row) + 2 * id[v]) = sum[v];
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    }
-}
+#define IRPE_SCATTER_GROUP 4
+#endif
 
 template <int K> using Slot = std::integral_constant<int, K>;
 constexpr int PF = 1;       // streamed tiles in flight in registers.  Measured at L = 577: 3 in flight cost 48 more VGPRs
@@ -266,51 +201,6 @@ template <int LBP> __device__ __forceinline__ void bias_rows_to_lds(short* scr, 
 #pragma unroll 8
     for (int e = 0; e < 32; ++e)
         if (LBP >= 64 || g * 32 + e < LBP) row[e] = f2bf(g * 32 + e < nb ? bias[g * 32 + e] : 0.f);
-}
-
-// this lane's half of a bf16 lookup row (buckets ks*16 + g*8 .. +7, ks = 0..3) -> global row of 64
-__device__ __forceinline__ void lrow_to_global(short* dst, const short* row, int g) {
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-        const uint32_t* s = reinterpret_cast<const uint32_t*>(row + ks * 16 + g * 8);
-        *reinterpret_cast<u32x4v*>(dst + ks * 16 + g * 8) = u32x4v{s[0], s[1], s[2], s[3]};
-    }
-}
-// fragment of 8 consecutive values (buckets ks*16 + g*8 ..) of an fp32 scatter-add row, times mul
-template <int LKP> __device__ __forceinline__ F srow_frag(const float* row, int ks, int g, float mul) {
-    f32x8v x;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) x[e] = (LKP >= 64 || ks * 16 + g * 8 + e < LKP) ? row[ks * 16 + g * 8 + e] * mul : 0.f;
-    return __builtin_bit_cast(F, __builtin_convertvector(x, hwbf16x8));
-}
-__device__ __forceinline__ void store_row64(short* op, const f32x16 (&o)[2], int g, float mul) {
-#pragma unroll
-    for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-        for (int r4 = 0; r4 < 4; ++r4) {
-            const int d = dt * 32 + 8 * r4 + 4 * g;
-            *reinterpret_cast<u32x2v*>(op + d) = u32x2v{f2bf_pair(o[dt][4 * r4] * mul, o[dt][4 * r4 + 1] * mul),
-                                                        f2bf_pair(o[dt][4 * r4 + 2] * mul, o[dt][4 * r4 + 3] * mul)};
-        }
-}
-__device__ __forceinline__ void load_frags(F (&f)[4], const short* row, int g) {
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) f[ks] = TT::load(row + ks * 16 + g * 8);
-}
-
-// A operand of a product that contracts over the 32 streamed tokens of a ROW-major [32][KP] tile (rows = tokens):
-// MFMA row = column dt*32 + (lane & 31) of the tile, contraction indices in the permuted order of from_acc
-// (acc_row(s2*8 + e, g)): two ds_read_b64_tr_b16 — the transpose happens on the way to the matrix cores, so no
-// transposed copy of the tile is staged (8 conflicting 2-byte LDS stores per thread and tile, and 9 KB per buffer).
-__device__ __forceinline__ F load_perm_tr(const short* rows, int dt, int s2, int lane) {
-    typedef short s16x4 __attribute__((ext_vector_type(4)));
-    const int gi = lane & 15, q = lane >> 4;
-    const short* p0 = rows + (16 * s2 + 4 * (q >> 1) + (gi >> 2)) * KP + dt * 32 + 16 * (q & 1) + (gi & 3) * 4;
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-        reinterpret_cast<__attribute__((address_space(3))) s16x4*>(reinterpret_cast<uintptr_t>(p0)));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-        reinterpret_cast<__attribute__((address_space(3))) s16x4*>(reinterpret_cast<uintptr_t>(p0 + 8 * KP)));
-    return F{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -513,10 +403,10 @@ __global__ __launch_bounds__(256) void irpe_attn_fwd_kernel(const Args a) {     
 #pragma unroll
                 for (int s2 = 0; s2 < 2; ++s2) {
                     const F pb = TT::from_acc(s, s2);
-                    o[0] = TT::mma(load_perm_tr(vb, 0, s2, lane), pb, o[0]);
-                    o[1] = TT::mma(load_perm_tr(vb, 1, s2, lane), pb, o[1]);
+                    o[0] = TT::mma(load_perm_tr<KP>(vb, 0, s2, lane), pb, o[0]);
+                    o[1] = TT::mma(load_perm_tr<KP>(vb, 1, s2, lane), pb, o[1]);
                 }
-                if constexpr (HV) scatter_add16(svw + c32 * LKP, civ, s, g);
+                if constexpr (HV) scatter_add16<IRPE_SCATTER_GROUP>(svw + c32 * LKP, civ, s, g);
             }
             if (more) {
                 rows_store(kbuf + nxt * 32 * KP, sk);
@@ -556,7 +446,7 @@ __global__ __launch_bounds__(256) void irpe_attn_fwd_kernel(const Args a) {     
             o[1] = TT::mma(TT::load(wvT + (c32 + 32) * KP + ks * 16 + g * 8), sb, o[1]);
         }
     }
-    if (qok) store_row64(a.out + (((int64_t)b * a.L + qi) * a.H + h) * 64, o, g, 1.f);
+    if (qok) store_row(a.out + (((int64_t)b * a.L + qi) * a.H + h) * 64, o, g, 1.f);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -659,12 +549,12 @@ __global__ __launch_bounds__(256) void irpe_attn_bwd_q_kernel(const Args a) {   
             if (a.wk) lookups_to_lds<LBP>(lkw, tab0, qs, 1.f, lane);
             else bias_rows_to_lds<LBP>(lkw, a.bk + (int64_t)h * a.bk_hs, a.nb, lane);
             wave_lds_fence();
-            lrow_to_global(a.lkg + ((int64_t)bh * a.NP + qi) * 64, lkw + c32 * LBP, g);
+            lrow_to_global<4>(a.lkg + ((int64_t)bh * a.NP + qi) * 64, lkw + c32 * LBP, g);
         }
         if constexpr (HV) {
             lookups_to_lds<LBP>(glw, tab1, dob, 1.f, lane);
             wave_lds_fence();
-            lrow_to_global(a.gg + ((int64_t)bh * a.NP + qi) * 64, glw + c32 * LBP, g);
+            lrow_to_global<4>(a.gg + ((int64_t)bh * a.NP + qi) * 64, glw + c32 * LBP, g);
         }
     }
     __syncthreads();                                   // tables consumed: the tile area is free
@@ -723,13 +613,13 @@ __global__ __launch_bounds__(256) void irpe_attn_bwd_q_kernel(const Args a) {   
                 if constexpr (DROP) dpr = drop_keep(drop_key(a.drop_seed, bh), qi, key, a.drop_thr) ? dpr * a.drop_scale : 0.f;
                 s[r] = p * (dpr - delta);
             }
-            if constexpr (HK) scatter_add16(dlkw + c32 * LKP, cik, s, g);
+            if constexpr (HK) scatter_add16<IRPE_SCATTER_GROUP>(dlkw + c32 * LKP, cik, s, g);
             const short* kb = kbuf + cur * 32 * KP;
 #pragma unroll
             for (int s2 = 0; s2 < 2; ++s2) {
                 const F db = TT::from_acc(s, s2);
-                dq[0] = TT::mma(load_perm_tr(kb, 0, s2, lane), db, dq[0]);
-                dq[1] = TT::mma(load_perm_tr(kb, 1, s2, lane), db, dq[1]);
+                dq[0] = TT::mma(load_perm_tr<KP>(kb, 0, s2, lane), db, dq[0]);
+                dq[1] = TT::mma(load_perm_tr<KP>(kb, 1, s2, lane), db, dq[1]);
             }
         }
         if (t + 1 < NT) {
@@ -761,7 +651,7 @@ __global__ __launch_bounds__(256) void irpe_attn_bwd_q_kernel(const Args a) {   
             }
         }
     }
-    if (qok) store_row64(a.dq + (int64_t)b * a.dsb + (int64_t)qi * a.dsn + (int64_t)h * a.dsh, dq, g, a.scale);
+    if (qok) store_row(a.dq + (int64_t)b * a.dsb + (int64_t)qi * a.dsn + (int64_t)h * a.dsh, dq, g, a.scale);
 }
 
 // rpe_q lookup rows of every key, (k * scale) Wq as bf16 (the values lq_tile puts in LDS in the forward: product first, scale
@@ -783,7 +673,7 @@ __global__ __launch_bounds__(256) void irpe_lq_rows_kernel(const Args a, short* 
     short* rows = scr + wave * 32 * 66;
     lookups_to_lds<66>(rows, tab, kf, a.scale, lane);
     wave_lds_fence();
-    lrow_to_global(dst + ((int64_t)bh * a.NP + kj) * 64, rows + c32 * 66, g);
+    lrow_to_global<4>(dst + ((int64_t)bh * a.NP + kj) * 64, rows + c32 * 66, g);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -930,16 +820,16 @@ __global__ __launch_bounds__(256) void irpe_attn_bwd_kv_kernel(const Args a) {  
                     ds[r] = p * (dpr - dl[e]);
                 }
             }
-            if constexpr (HQ) scatter_add16(dlqw + c32 * LKP, ciq, ds, g);
+            if constexpr (HQ) scatter_add16<IRPE_SCATTER_GROUP>(dlqw + c32 * LKP, ciq, ds, g);
             const short* qb = qbuf + cur * 32 * KP;
 #pragma unroll
             for (int s2 = 0; s2 < 2; ++s2) {
                 const F pb = TT::from_acc(s, s2);
                 const F sb = TT::from_acc(ds, s2);
-                dv[0] = TT::mma(load_perm_tr(db, 0, s2, lane), pb, dv[0]);
-                dv[1] = TT::mma(load_perm_tr(db, 1, s2, lane), pb, dv[1]);
-                dk[0] = TT::mma(load_perm_tr(qb, 0, s2, lane), sb, dk[0]);
-                dk[1] = TT::mma(load_perm_tr(qb, 1, s2, lane), sb, dk[1]);
+                dv[0] = TT::mma(load_perm_tr<KP>(db, 0, s2, lane), pb, dv[0]);
+                dv[1] = TT::mma(load_perm_tr<KP>(db, 1, s2, lane), pb, dv[1]);
+                dk[0] = TT::mma(load_perm_tr<KP>(qb, 0, s2, lane), sb, dk[0]);
+                dk[1] = TT::mma(load_perm_tr<KP>(qb, 1, s2, lane), sb, dk[1]);
             }
         }
         if (t + 1 < NT) {
@@ -972,8 +862,8 @@ __global__ __launch_bounds__(256) void irpe_attn_bwd_kv_kernel(const Args a) {  
     }
     if (kok) {
         const int64_t off = (int64_t)b * a.dsb + (int64_t)kj * a.dsn + (int64_t)h * a.dsh;
-        store_row64(a.dk + off, dk, g, 1.f);
-        store_row64(a.dv + off, dv, g, 1.f);
+        store_row(a.dk + off, dk, g, 1.f);
+        store_row(a.dv + off, dv, g, 1.f);
     }
 }
 

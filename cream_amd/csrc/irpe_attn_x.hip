@@ -7,7 +7,8 @@
 // (cream_irpe_bucket_bytes: ids up to 127 fit), lookup rows in LDS, ordered read-modify-write scatter rows, forward with
 // a lazy running maximum, backward launch A over queries, launch B over keys, pre-pass for the rpe_q rows, per-(b, h)
 // table-gradient products, no global atomics, fixed summation order.  The 64-wide / <= 64-bucket / unmasked kernels of
-// irpe_attn.hip are NOT touched by this file: it is a sibling with its own entry points (cream_irpe_attn2_*).
+// irpe_attn.hip are NOT touched by this file: it is a sibling with its own entry points (cream_irpe_attn2_*).  The two share
+// their lane-level helpers (bucket ids, scatter-add, operand fragments, output rows) through attn_lane.hpp and nothing else.
 //
 // What is a template parameter here:
 //   D    head_dim 32 | 64.  Row tiles are [32][D] with pitch D + 8 (80 / 144 bytes: 16-byte reads of 8 consecutive rows
@@ -33,13 +34,11 @@
 
 #include <type_traits>
 
-#include "attn_common.hpp"
+#include "attn_lane.hpp"
 #include "cream_amd.h"
 
 namespace {
 using namespace cream;
-using TT = Tr<hip_bfloat16>;
-using F = TT::frag;
 
 constexpr float LOG2E = 1.4426950408889634f;
 constexpr int QW = 4;       // waves (32-token tiles) per workgroup
@@ -90,22 +89,6 @@ struct Args {
     short *lkg, *gg;                  // (B, H, NP, NBW)
     short *dlk, *dlq;                 // (B, H, NP, NBW)
 };
-
-// consecutive logical workgroups (the blocks of one (b,h), which share the streamed side) on one XCD
-__device__ __forceinline__ int xcd_order(int bid, int n) {
-    if (n & 7) return bid;
-    return (bid & 7) * (n >> 3) + (bid >> 3);
-}
-
-__device__ __forceinline__ F scaled(const F x, float s) {
-    f32x8v y;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) y[e] = bf2f(x[e]) * s;
-    return __builtin_bit_cast(F, __builtin_convertvector(y, hwbf16x8));
-}
-__device__ __forceinline__ u32x4v scaled_raw(const u32x4v x, float s) {
-    return __builtin_bit_cast(u32x4v, scaled(__builtin_bit_cast(F, x), s));
-}
 
 // dst[c][r] = src[r][c] for r < R, c < C (src: nrow x ncol fp32, zero outside) as bf16 operand rows of pitch P
 template <int R, int C, int P> __device__ __forceinline__ void stage_T(short* dst, const float* src, int nrow, int ncol) {
@@ -183,18 +166,6 @@ template <int W, int P> __device__ __forceinline__ void rows_store_T(short* dst,
     }
 }
 
-// the 16 bucket ids of this lane's (own row, partners acc_row(r, g)) of streamed tile t: one 16-byte load (irpe_attn.hip)
-__device__ __forceinline__ u32x4v ids_load(const uint8_t* tab, int NP, int row, int t, int g) {
-    return *reinterpret_cast<const u32x4v*>(tab + (int64_t)min(row, NP - 1) * NP + t * 32 + g * 16);
-}
-// the bytes hold 2 * bucket id (<= 254): the byte offset of the bucket in a bf16 lookup row
-__device__ __forceinline__ int off2_of(const u32x4v& w, int r) { return (w[r >> 2] >> (8 * (r & 3))) & 0xffu; }
-typedef __bf16 hwbf16x2v __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ float add_bf16_at(float acc, const short* row, int off2) {
-    const uint32_t x = *reinterpret_cast<const unsigned short*>(reinterpret_cast<const char*>(row) + off2);
-    return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(hwbf16x2v, x), __builtin_bit_cast(hwbf16x2v, 0x3F803F80u), acc, false);
-}
-
 // the image's key mask as NP bytes in LDS: 1 = the key takes no part (padded by the caller, or the tail j >= L)
 __device__ __forceinline__ void stage_pad(uint8_t* dst, const Args& a, int b) {
     for (int i = threadIdx.x; i < a.NP; i += 256)
@@ -210,37 +181,6 @@ __device__ __forceinline__ uint32_t pad_bits(const uint8_t* padm, int t, int g) 
         for (int e = 0; e < 4; ++e) m |= ((w >> (8 * e)) & 0xffu) ? (1u << (4 * rr + e)) : 0u;
     }
     return m;
-}
-
-// row[id_r] += val_r for the 16 (bucket id, value) pairs of this lane, ordered read-modify-write (irpe_attn.hip scatter_add16)
-constexpr int SCATTER_GROUP = 4;
-__device__ __forceinline__ void scatter_add16(float* row, const u32x4v& w, const f32x16& val, int g) {
-    constexpr int G = SCATTER_GROUP;
-#pragma unroll
-    for (int half = 0; half < 2; ++half) {
-        if (g == half) {
-#pragma unroll
-            for (int grp = 0; grp < 16 / G; ++grp) {
-                int id[G];
-                float sum[G];
-#pragma unroll
-                for (int v = 0; v < G; ++v) {
-                    id[v] = off2_of(w, grp * G + v);
-                    sum[v] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(row) + 2 * id[v]);
-                }
-#pragma unroll
-                for (int v = 0; v < G; ++v) {
-                    float base = sum[v];
-#pragma unroll
-                    for (int u = 0; u < v; ++u) base = (id[u] == id[v]) ? sum[u] : base;
-                    sum[v] = base + val[grp * G + v];
-                }
-#pragma unroll
-                for (int v = 0; v < G; ++v) *reinterpret_cast<float*>(reinterpret_cast<char*>(row) + 2 * id[v]) = sum[v];
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    }
 }
 
 // lookups^T (NBW buckets x 32 own rows) = tab(NBW buckets x D) . X^T  ->  scr[row][bucket] (bf16) * mul
@@ -264,48 +204,6 @@ template <typename G> __device__ __forceinline__ void bias_rows_to_lds(short* sc
 #pragma unroll 8
     for (int e = 0; e < HALF; ++e) row[e] = f2bf(g * HALF + e < nb ? bias[g * HALF + e] : 0.f);
 }
-// this lane's half of a bf16 lookup row (buckets ks*16 + g*8 .. +7) -> global row of NBW
-template <typename G> __device__ __forceinline__ void lrow_to_global(short* dst, const short* row, int g) {
-#pragma unroll
-    for (int ks = 0; ks < G::KSB; ++ks) {
-        const uint32_t* s = reinterpret_cast<const uint32_t*>(row + ks * 16 + g * 8);
-        *reinterpret_cast<u32x4v*>(dst + ks * 16 + g * 8) = u32x4v{s[0], s[1], s[2], s[3]};
-    }
-}
-// fragment of 8 consecutive values (buckets ks*16 + g*8 ..) of an fp32 scatter-add row, times mul
-__device__ __forceinline__ F srow_frag(const float* row, int ks, int g, float mul) {
-    f32x8v x;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) x[e] = row[ks * 16 + g * 8 + e] * mul;
-    return __builtin_bit_cast(F, __builtin_convertvector(x, hwbf16x8));
-}
-template <int DT> __device__ __forceinline__ void store_row(short* op, const f32x16 (&o)[DT], int g, float mul) {
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-        for (int r4 = 0; r4 < 4; ++r4) {
-            const int d = dt * 32 + 8 * r4 + 4 * g;
-            *reinterpret_cast<u32x2v*>(op + d) = u32x2v{f2bf_pair(o[dt][4 * r4] * mul, o[dt][4 * r4 + 1] * mul),
-                                                        f2bf_pair(o[dt][4 * r4 + 2] * mul, o[dt][4 * r4 + 3] * mul)};
-        }
-}
-template <int KS> __device__ __forceinline__ void load_frags(F (&f)[KS], const short* row, int g) {
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) f[ks] = TT::load(row + ks * 16 + g * 8);
-}
-
-// A operand of a product that contracts over the 32 streamed tokens of a ROW-major [32][KP] tile: ds_read_b64_tr_b16 (irpe_attn.hip)
-template <int KP> __device__ __forceinline__ F load_perm_tr(const short* rows, int dt, int s2, int lane) {
-    typedef short s16x4 __attribute__((ext_vector_type(4)));
-    const int gi = lane & 15, q = lane >> 4;
-    const short* p0 = rows + (16 * s2 + 4 * (q >> 1) + (gi >> 2)) * KP + dt * 32 + 16 * (q & 1) + (gi & 3) * 4;
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-        reinterpret_cast<__attribute__((address_space(3))) s16x4*>(reinterpret_cast<uintptr_t>(p0)));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-        reinterpret_cast<__attribute__((address_space(3))) s16x4*>(reinterpret_cast<uintptr_t>(p0 + 8 * KP)));
-    return F{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-}
-
 // S^T tile (rows = streamed tokens, column = own token) with the relative position terms (irpe_attn.hip score_tile)
 template <typename G, bool OWN, bool SIDE>
 __device__ __forceinline__ f32x16 score_tile(const short* rows, const F (&own)[G::KS], const u32x4v& own_ids,
@@ -527,7 +425,7 @@ __global__ __launch_bounds__(256) void irpe_x_fwd_kernel(const Args a) {
         short* svg = a.sv + ((int64_t)bh * a.NP + qi) * G::NBW;
 #pragma unroll
         for (int ks = 0; ks < G::KSB; ++ks) {
-            const F sb = srow_frag(row, ks, g, inv_l);
+            const F sb = srow_frag<LKP>(row, ks, g, inv_l);
             *reinterpret_cast<F*>(svg + ks * 16 + g * 8) = sb;
 #pragma unroll
             for (int dt = 0; dt < DT; ++dt) o[dt] = TT::mma(TT::load(wvT + (c32 + 32 * dt) * G::WP + ks * 16 + g * 8), sb, o[dt]);
@@ -627,12 +525,12 @@ __global__ __launch_bounds__(256) void irpe_x_bwd_q_kernel(const Args a) {
             if (a.wk) lookups_to_lds<G>(lkw, tab0, qs, 1.f, lane);
             else bias_rows_to_lds<G>(lkw, a.bk + (int64_t)h * a.bk_hs, a.nb, lane);
             wave_lds_fence();
-            lrow_to_global<G>(a.lkg + ((int64_t)bh * a.NP + qi) * NBW, lkw + c32 * LBP, g);
+            lrow_to_global<G::KSB>(a.lkg + ((int64_t)bh * a.NP + qi) * NBW, lkw + c32 * LBP, g);
         }
         if constexpr (HV) {
             lookups_to_lds<G>(glw, tab1, dob, 1.f, lane);
             wave_lds_fence();
-            lrow_to_global<G>(a.gg + ((int64_t)bh * a.NP + qi) * NBW, glw + c32 * LBP, g);
+            lrow_to_global<G::KSB>(a.gg + ((int64_t)bh * a.NP + qi) * NBW, glw + c32 * LBP, g);
         }
     }
     __syncthreads();                                   // tables consumed: the tile area is free
@@ -715,7 +613,7 @@ __global__ __launch_bounds__(256) void irpe_x_bwd_q_kernel(const Args a) {
             short* dst = a.dlk + ((int64_t)bh * a.NP + qi) * NBW;
 #pragma unroll
             for (int ks = 0; ks < G::KSB; ++ks) {
-                const F db = srow_frag(row, ks, g, 1.f);
+                const F db = srow_frag<LKP>(row, ks, g, 1.f);
                 *reinterpret_cast<F*>(dst + ks * 16 + g * 8) = db;
                 if (ctx) {
 #pragma unroll
@@ -747,7 +645,7 @@ __global__ __launch_bounds__(256) void irpe_x_lq_rows_kernel(const Args a, short
     short* rows = scr + wave * 32 * G::LB;
     lookups_to_lds<G>(rows, tab, kf, a.scale, lane);
     wave_lds_fence();
-    lrow_to_global<G>(dst + ((int64_t)bh * a.NP + kj) * G::NBW, rows + c32 * G::LB, g);
+    lrow_to_global<G::KSB>(dst + ((int64_t)bh * a.NP + kj) * G::NBW, rows + c32 * G::LB, g);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -923,9 +821,9 @@ __global__ __launch_bounds__(256) void irpe_x_bwd_kv_kernel(const Args a) {
             short* dst = a.dlq + ((int64_t)bh * a.NP + kj) * NBW;
 #pragma unroll
             for (int ks = 0; ks < G::KSB; ++ks) {
-                *reinterpret_cast<F*>(dst + ks * 16 + g * 8) = srow_frag(row, ks, g, 1.f);
+                *reinterpret_cast<F*>(dst + ks * 16 + g * 8) = srow_frag<LKP>(row, ks, g, 1.f);
                 if (ctx) {
-                    const F db = srow_frag(row, ks, g, a.scale);
+                    const F db = srow_frag<LKP>(row, ks, g, a.scale);
 #pragma unroll
                     for (int dt = 0; dt < DT; ++dt) dk[dt] = TT::mma(TT::load(tab0 + (c32 + 32 * dt) * G::WP + ks * 16 + g * 8), db, dk[dt]);
                 }

@@ -19,7 +19,8 @@
 // wave-uniform scalars.  (An MFMA with heads as the contraction would need the heads on the lane axis, i.e. a transposing
 // exchange for a contraction of at most 12; the VALU form needs no relayout.)  The streamed side (K, V, or q, dO for the
 // key-owned launch) comes straight from global memory as the A operand (16 bytes per lane, L2-resident); only the tiles that
-// are contracted over their ROWS (P'.V, dS.K, ...) are staged, per wave, for the transposing LDS read.
+// are contracted over their ROWS (P'.V, dS.K, ...) are staged, per wave, for the transposing LDS read.  The exchange
+// (xchg_put / xchg_mix) and the bucket-id and scatter-add helpers are in attn_lane.hpp.
 //
 // Forward: two passes over the keys (pass 1: running max / sum of S' per (o, i); pass 2: P from the final statistics, P', P'.V) —
 // conv_w mixes rows normalised by different sums, so a one-pass online softmax would need H^2 cross accumulators.
@@ -39,13 +40,11 @@
 #include <hip/hip_bfloat16.h>
 #include <stdint.h>
 
-#include "attn_common.hpp"
+#include "attn_lane.hpp"
 #include "cream_amd.h"
 
 namespace {
 using namespace cream;
-using TT = Tr<hip_bfloat16>;
-using F = TT::frag;
 
 constexpr float LOG2E = 1.4426950408889634f;
 constexpr int KP = 72;      // pitch (bf16) of staged row-major [32][64] tiles
@@ -73,68 +72,15 @@ struct Args {
     int slot;                         // launch Q: the head slot whose dq / dLK this launch produces
 };
 
-__device__ __forceinline__ F scaled(const F x, float s) {
-    f32x8v y;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) y[e] = bf2f(x[e]) * s;
-    return __builtin_bit_cast(F, __builtin_convertvector(y, hwbf16x8));
-}
-__device__ __forceinline__ void load_frags(F (&f)[4], const short* row, int g) {
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) f[ks] = TT::load(row + ks * 16 + g * 8);
-}
 __device__ __forceinline__ void load_frags_scaled(F (&f)[4], const short* row, int g, float s) {
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) f[ks] = scaled(TT::load(row + ks * 16 + g * 8), s);
 }
-// the 16 bucket ids (as byte offsets 2 * id into a bf16 lookup row) of (own row, partners acc_row(r, g) of streamed tile t)
-__device__ __forceinline__ u32x4v ids_load(const uint8_t* tab, int NP, int row, int t, int g) {
-    return *reinterpret_cast<const u32x4v*>(tab + (int64_t)min(row, NP - 1) * NP + t * 32 + g * 16);
-}
-__device__ __forceinline__ int off2_of(const u32x4v& w, int r) { return (w[r >> 2] >> (8 * (r & 3))) & 0xffu; }
-__device__ __forceinline__ float add_bf16_at(float acc, const short* row, int off2) {
+// acc += (bf16 at byte offset off2 of row) as shift + add: attn_lane.hpp's add_bf16_at (v_dot2c) is another instruction sequence,
+// and these kernels were measured with this one
+__device__ __forceinline__ float add_bf16_at_shift(float acc, const short* row, int off2) {
     const uint32_t x = *reinterpret_cast<const unsigned short*>(reinterpret_cast<const char*>(row) + off2);
     return acc + __uint_as_float(x << 16);
-}
-// row[id_r] += val_r for the 16 (bucket, value) pairs of this lane, no LDS atomics: the two lanes of a row take turns, four
-// pairs at a time with duplicates resolved in registers (the scheme of irpe_attn.hip)
-__device__ __forceinline__ void scatter_add16(float* row, const u32x4v& w, const f32x16& val, int g) {
-    constexpr int G = 4;
-#pragma unroll
-    for (int half = 0; half < 2; ++half) {
-        if (g == half) {
-#pragma unroll
-            for (int grp = 0; grp < 16 / G; ++grp) {
-                int id[G];
-                float sum[G];
-#pragma unroll
-                for (int v = 0; v < G; ++v) {
-                    id[v] = off2_of(w, grp * G + v);
-                    sum[v] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(row) + 2 * id[v]);
-                }
-#pragma unroll
-                for (int v = 0; v < G; ++v) {
-                    float base = sum[v];
-#pragma unroll
-                    for (int u = 0; u < v; ++u) base = (id[u] == id[v]) ? sum[u] : base;
-                    sum[v] = base + val[grp * G + v];
-                }
-#pragma unroll
-                for (int v = 0; v < G; ++v) *reinterpret_cast<float*>(reinterpret_cast<char*>(row) + 2 * id[v]) = sum[v];
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    }
-}
-__device__ __forceinline__ void store_row64(short* op, const f32x16 (&o)[2], int g, float mul) {
-#pragma unroll
-    for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-        for (int r4 = 0; r4 < 4; ++r4) {
-            const int d = dt * 32 + 8 * r4 + 4 * g;
-            *reinterpret_cast<u32x2v*>(op + d) = u32x2v{f2bf_pair(o[dt][4 * r4] * mul, o[dt][4 * r4 + 1] * mul),
-                                                        f2bf_pair(o[dt][4 * r4 + 2] * mul, o[dt][4 * r4 + 3] * mul)};
-        }
 }
 
 // tile^T (rows = 32 streamed tokens from row0, column = own token) = A rows (global, 64 wide, clamped to the last real row) . own^T
@@ -197,72 +143,6 @@ __device__ __forceinline__ void lookups_to_lds(short* rows, const float* wk, int
         row[32 + acc_row(r, g)] = f2bf(a1[r]);
     }
 }
-__device__ __forceinline__ void lrow_to_global(short* dst, const short* row, int g) {
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-        const uint32_t* s = reinterpret_cast<const uint32_t*>(row + ks * 16 + g * 8);
-        *reinterpret_cast<u32x4v*>(dst + ks * 16 + g * 8) = u32x4v{s[0], s[1], s[2], s[3]};
-    }
-}
-
-// ---- the exchange: X[h][r4][lane] (16 bytes each) holds the tile of head h in the accumulator layout -----------------------
-template <int HPW>
-__device__ __forceinline__ void xchg_put(float* X, const f32x16 (&in)[HPW], int H, int wave, int lane) {
-    __syncthreads();                                   // every wave has read the previous contents
-#pragma unroll
-    for (int s = 0; s < HPW; ++s) {
-        const int h = wave + 4 * s;
-        if (h < H) {
-#pragma unroll
-            for (int r4 = 0; r4 < 4; ++r4)
-                *reinterpret_cast<f32x4v*>(X + ((h * 4 + r4) * 64 + lane) * 4) =
-                    f32x4v{in[s][4 * r4], in[s][4 * r4 + 1], in[s][4 * r4 + 2], in[s][4 * r4 + 3]};
-        }
-    }
-    __syncthreads();
-}
-// out[s] = sum_h W[o_s][h] X[h]  (TRANS: sum_h W[h][o_s] X[h]);  CROSS: cross[h][s] += sum over this lane's 16 elements of
-// own[s] * X[h]  (the lane's share of a weight gradient: row h = the exchanged head, column = the own head of slot s)
-template <int HPW, bool TRANS, bool CROSS>
-__device__ __forceinline__ void xchg_mix(const float* X, f32x16 (&out)[HPW], const float* __restrict__ W, int H, int wave, int lane,
-                                         const f32x16 (&own)[HPW], float (&cross)[4 * HPW][HPW]) {
-#pragma unroll
-    for (int s = 0; s < HPW; ++s) out[s] = f32x16{};
-#pragma unroll
-    for (int h = 0; h < 4 * HPW; ++h) {
-        if (h < H) {
-            f32x16 x;
-#pragma unroll
-            for (int r4 = 0; r4 < 4; ++r4) {
-                const f32x4v v = *reinterpret_cast<const f32x4v*>(X + ((h * 4 + r4) * 64 + lane) * 4);
-                x[4 * r4] = v[0]; x[4 * r4 + 1] = v[1]; x[4 * r4 + 2] = v[2]; x[4 * r4 + 3] = v[3];
-            }
-#pragma unroll
-            for (int s = 0; s < HPW; ++s) {
-                const int o = wave + 4 * s;
-                if (o < H) {
-                    const float w = TRANS ? W[h * H + o] : W[o * H + h];
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) out[s][r] = __builtin_fmaf(w, x[r], out[s][r]);
-                    if constexpr (CROSS) {
-                        float c0 = 0.f, c1 = 0.f;
-#pragma unroll
-                        for (int r = 0; r < 16; r += 2) {
-                            c0 = __builtin_fmaf(own[s][r], x[r], c0);
-                            c1 = __builtin_fmaf(own[s][r + 1], x[r + 1], c1);
-                        }
-                        cross[h][s] += c0 + c1;
-                    }
-                }
-            }
-        }
-    }
-}
-template <int HPW, bool TRANS>
-__device__ __forceinline__ void xchg_mix(const float* X, f32x16 (&out)[HPW], const float* __restrict__ W, int H, int wave, int lane) {
-    float dummy[4 * HPW][HPW];
-    xchg_mix<HPW, TRANS, false>(X, out, W, H, wave, lane, out, dummy);
-}
 // the lanes' shares of a weight gradient -> part[row h][column own head], summed over the wave in a fixed butterfly
 template <int HPW>
 __device__ __forceinline__ void cross_store(float* part, float (&cross)[4 * HPW][HPW], int H, int wave, int lane) {
@@ -272,7 +152,7 @@ __device__ __forceinline__ void cross_store(float* part, float (&cross)[4 * HPW]
         for (int s = 0; s < HPW; ++s) {
             float v = cross[h][s];
 #pragma unroll
-            for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+            for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);        // (wave_sum of lane_ops.hpp, kept inline: the call form schedules these kernels differently)
             const int o = wave + 4 * s;
             if (h < H && o < H && lane == 0) part[h * H + o] = v;
         }
@@ -302,7 +182,7 @@ __device__ __forceinline__ void own_scores(f32x16 (&S)[HPW], const Args& a, cons
             if constexpr (HK) {
                 const short* row = lk + (h * 32 + c32) * LBP;
 #pragma unroll
-                for (int r = 0; r < 16; ++r) S[s][r] = add_bf16_at(S[s][r], row, off2_of(ids, r));
+                for (int r = 0; r < 16; ++r) S[s][r] = add_bf16_at_shift(S[s][r], row, off2_of(ids, r));
             }
         }
     }
@@ -319,7 +199,7 @@ __device__ __forceinline__ void own_lookups(short* lk, const Args& a, const shor
             load_frags_scaled(qs, qp + (int64_t)min(qi, a.L - 1) * a.sn + (int64_t)h * a.sh, g, a.scale);
             lookups_to_lds(lk + h * 32 * LBP, a.wk + (int64_t)h * a.wk_hs, a.nb, qs, lane);
             wave_lds_fence();
-            if (to_global) lrow_to_global(a.lkg + (((int64_t)b * a.H + h) * a.NP + qi) * 64, lk + (h * 32 + c32) * LBP, g);
+            if (to_global) lrow_to_global<4>(a.lkg + (((int64_t)b * a.H + h) * a.NP + qi) * 64, lk + (h * 32 + c32) * LBP, g);
         }
     }
 }
@@ -354,7 +234,7 @@ __global__ __launch_bounds__(256) void mini_attn_fwd_kernel(const Args a) {
         u32x4v ids = {};
         if constexpr (HK) ids = ids_load(a.idk, a.NP, qi, t, g);
         own_scores<HPW, HK>(S, a, qp, kp, lk, qi, t, ids, wave, lane);
-        xchg_put<HPW>(X, S, a.H, wave, lane);
+        xchg_put<HPW>(X, S, 0, a.H, wave, lane);
         xchg_mix<HPW, false>(X, Sp, a.wl, a.H, wave, lane);
 #pragma unroll
         for (int s = 0; s < HPW; ++s) {
@@ -392,14 +272,14 @@ __global__ __launch_bounds__(256) void mini_attn_fwd_kernel(const Args a) {
         u32x4v ids = {};
         if constexpr (HK) ids = ids_load(a.idk, a.NP, qi, t, g);
         own_scores<HPW, HK>(S, a, qp, kp, lk, qi, t, ids, wave, lane);
-        xchg_put<HPW>(X, S, a.H, wave, lane);
+        xchg_put<HPW>(X, S, 0, a.H, wave, lane);
         xchg_mix<HPW, false>(X, Sp, a.wl, a.H, wave, lane);
 #pragma unroll
         for (int s = 0; s < HPW; ++s)
 #pragma unroll
             for (int r = 0; r < 16; ++r)
                 Sp[s][r] = t * 32 + acc_row(r, g) < a.L ? __builtin_amdgcn_exp2f((Sp[s][r] - lse[s]) * LOG2E) : 0.f;
-        xchg_put<HPW>(X, Sp, a.H, wave, lane);
+        xchg_put<HPW>(X, Sp, 0, a.H, wave, lane);
         xchg_mix<HPW, false>(X, S, a.ww, a.H, wave, lane);                         // S now holds P'
 #pragma unroll
         for (int s = 0; s < HPW; ++s) {
@@ -413,7 +293,7 @@ __global__ __launch_bounds__(256) void mini_attn_fwd_kernel(const Args a) {
 #pragma unroll
     for (int s = 0; s < HPW; ++s) {
         const int o = wave + 4 * s;
-        if (o < a.H && qok) store_row64(a.out + (((int64_t)b * a.L + qi) * a.H + o) * 64, O[s], g, 1.f);
+        if (o < a.H && qok) store_row(a.out + (((int64_t)b * a.L + qi) * a.H + o) * 64, O[s], g, 1.f);
     }
 }
 
@@ -466,7 +346,7 @@ __global__ __launch_bounds__(256) void mini_attn_bwd_q_kernel(const Args a) {
         u32x4v ids = {};
         if constexpr (HK) ids = ids_load(a.idk, a.NP, qi, t, g);
         own_scores<HPW, HK>(S, a, qp, kp, lk, qi, t, ids, wave, lane);
-        xchg_put<HPW>(X, S, a.H, wave, lane);
+        xchg_put<HPW>(X, S, 0, a.H, wave, lane);
         xchg_mix<HPW, false>(X, P, a.wl, a.H, wave, lane);
 #pragma unroll
         for (int s = 0; s < HPW; ++s)
@@ -484,7 +364,7 @@ __global__ __launch_bounds__(256) void mini_attn_bwd_q_kernel(const Args a) {
                 T[s] = stream_tile(vp + (int64_t)o * a.sh, a.sn, t * 32, a.L, 1.f, false, df, lane);
             }
         }
-        xchg_put<HPW>(X, T, a.H, wave, lane);
+        xchg_put<HPW>(X, T, 0, a.H, wave, lane);
         if constexpr (MODE == 0) xchg_mix<HPW, true, true>(X, U, a.ww, a.H, wave, lane, P, cross);      // dP; dWw[o][h] += dP'_o P_h
         else xchg_mix<HPW, true>(X, U, a.ww, a.H, wave, lane);
         if constexpr (MODE == 0) {
@@ -503,7 +383,7 @@ __global__ __launch_bounds__(256) void mini_attn_bwd_q_kernel(const Args a) {
             for (int s = 0; s < HPW; ++s)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) T[s][r] = P[s][r] * (U[s][r] - dl[s]);                     // dS'
-            xchg_put<HPW>(X, T, a.H, wave, lane);
+            xchg_put<HPW>(X, T, 0, a.H, wave, lane);
             if (with_wl) xchg_mix<HPW, true, true>(X, U, a.wl, a.H, wave, lane, S, cross);              // dS; dWl[o][h] += dS'_o S_h
             else xchg_mix<HPW, true>(X, U, a.wl, a.H, wave, lane);
 #pragma unroll
@@ -553,7 +433,7 @@ __global__ __launch_bounds__(256) void mini_attn_bwd_q_kernel(const Args a) {
                     dq[1] = TT::mma(__builtin_bit_cast(F, __builtin_convertvector(w1, hwbf16x8)), xb, dq[1]);
                 }
             }
-            if (qok) store_row64(a.dq + (int64_t)b * a.dsb + (int64_t)qi * a.dsn + (int64_t)h * a.dsh, dq, g, a.scale);
+            if (qok) store_row(a.dq + (int64_t)b * a.dsb + (int64_t)qi * a.dsn + (int64_t)h * a.dsh, dq, g, a.scale);
         }
     }
 }
@@ -616,11 +496,11 @@ __global__ __launch_bounds__(256) void mini_attn_bwd_kv_kernel(const Args a) {
                 if constexpr (HK) {
 #pragma unroll
                     for (int r = 0; r < 16; ++r)
-                        S[s][r] = add_bf16_at(S[s][r], lk + (h * 32 + acc_row(r, g)) * LBP, off2_of(ids, r));
+                        S[s][r] = add_bf16_at_shift(S[s][r], lk + (h * 32 + acc_row(r, g)) * LBP, off2_of(ids, r));
                 }
             }
         }
-        xchg_put<HPW>(X, S, a.H, wave, lane);
+        xchg_put<HPW>(X, S, 0, a.H, wave, lane);
         xchg_mix<HPW, false>(X, P, a.wl, a.H, wave, lane);
 #pragma unroll
         for (int s = 0; s < HPW; ++s) {
@@ -630,7 +510,7 @@ __global__ __launch_bounds__(256) void mini_attn_bwd_kv_kernel(const Args a) {
                 P[s][r] = (kok && t * 32 + acc_row(r, g) < a.L)
                               ? __builtin_amdgcn_exp2f((P[s][r] - lse_s[o * 32 + acc_row(r, g)]) * LOG2E) : 0.f;
         }
-        xchg_put<HPW>(X, P, a.H, wave, lane);
+        xchg_put<HPW>(X, P, 0, a.H, wave, lane);
         xchg_mix<HPW, false>(X, S, a.ww, a.H, wave, lane);                         // P'
 #pragma unroll
         for (int s = 0; s < HPW; ++s) {
@@ -645,7 +525,7 @@ __global__ __launch_bounds__(256) void mini_attn_bwd_kv_kernel(const Args a) {
                 T[s] = stream_tile(dop + o * 64, dos, t * 32, a.L, 1.f, false, vf, lane);   // dP'_o
             }
         }
-        xchg_put<HPW>(X, T, a.H, wave, lane);
+        xchg_put<HPW>(X, T, 0, a.H, wave, lane);
         xchg_mix<HPW, true>(X, S, a.ww, a.H, wave, lane);                          // dP
 #pragma unroll
         for (int s = 0; s < HPW; ++s) {
@@ -653,7 +533,7 @@ __global__ __launch_bounds__(256) void mini_attn_bwd_kv_kernel(const Args a) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) T[s][r] = P[s][r] * (S[s][r] - dl_s[o * 32 + acc_row(r, g)]);   // dS'
         }
-        xchg_put<HPW>(X, T, a.H, wave, lane);
+        xchg_put<HPW>(X, T, 0, a.H, wave, lane);
         xchg_mix<HPW, true>(X, S, a.wl, a.H, wave, lane);                          // dS
 #pragma unroll
         for (int s = 0; s < HPW; ++s) {
@@ -669,8 +549,8 @@ __global__ __launch_bounds__(256) void mini_attn_bwd_kv_kernel(const Args a) {
     for (int s = 0; s < HPW; ++s) {
         const int h = wave + 4 * s;
         if (h < a.H && kok) {
-            store_row64(a.dk + (int64_t)b * a.dsb + (int64_t)kj * a.dsn + (int64_t)h * a.dsh, dk[s], g, 1.f);
-            store_row64(a.dv + (int64_t)b * a.dsb + (int64_t)kj * a.dsn + (int64_t)h * a.dsh, dv[s], g, 1.f);
+            store_row(a.dk + (int64_t)b * a.dsb + (int64_t)kj * a.dsn + (int64_t)h * a.dsh, dk[s], g, 1.f);
+            store_row(a.dv + (int64_t)b * a.dsb + (int64_t)kj * a.dsn + (int64_t)h * a.dsh, dv[s], g, 1.f);
         }
     }
 }

@@ -220,7 +220,7 @@ __global__ __launch_bounds__(256) void grad_sqnorm_kernel(const cream_param_job*
 #pragma unroll
             for (int e = 0; e < 4; ++e) s += gv[u][e] * gv[u][e];       // (elements outside the tensor are +0: they add nothing)
     }
-    double d = (double)s;
+    double d = (double)s;                       // (a double sum: not lane_ops.hpp's wave_sum(float))
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) d += __shfl_xor(d, off, 64);
     if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = d;

@@ -19,16 +19,12 @@
 #include <stdint.h>
 
 #include "attn_common.hpp"
+#include "lane_ops.hpp"
 #include "cream_amd.h"
 
 namespace {
 using namespace cream;
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 __device__ __forceinline__ void unpack_bf16x4(u32x2v v, float (&f)[4]) {
     f[0] = __uint_as_float(v[0] << 16); f[1] = __uint_as_float(v[0] & 0xFFFF0000u);
     f[2] = __uint_as_float(v[1] << 16); f[3] = __uint_as_float(v[1] & 0xFFFF0000u);

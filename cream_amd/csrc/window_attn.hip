@@ -18,8 +18,8 @@
 // [Hs-w, Hs-m), [Hs-m, Hs) with m = mask_shift.  (The reference applies a block's mask whether or not the repeat rolls the map,
 // so the roll and the mask are separate arguments.)  Nothing is read from an (N, N) index or mask matrix.
 //
-// Shape of the kernels (the scheme of mini_attn.hip with whole key rows on chip).  N <= 64, so a window's keys are at most two
-// 32-wide tiles.  A work item is (window, 32-query tile) with ALL heads; one workgroup = 4 waves, wave w owns heads w, w+4, ...
+// Shape of the kernels (all heads in one workgroup and the head exchange of attn_lane.hpp, as in mini_attn.hip, with whole key
+// rows on chip).  N <= 64, so a window's keys are at most two 32-wide tiles.  A work item is (window, 32-query tile) with ALL heads; one workgroup = 4 waves, wave w owns heads w, w+4, ...
 // (HPW head slots).  A wave computes the 32 x 32 tiles of its heads with the swapped product of attn_common.hpp (a lane holds 16
 // keys of ONE own query), the waves exchange tiles through the fp32 LDS buffer X[h][4][64 lanes][4] and every wave mixes the
 // tiles of all heads into those of its own heads on the VALU.  Both key tiles of the mixed logits stay in registers, so the
@@ -41,14 +41,12 @@
 #include <hip/hip_bfloat16.h>
 #include <stdint.h>
 
-#include "attn_common.hpp"
+#include "attn_lane.hpp"
 #include "cream_amd.h"
 #include "cu_budget.hpp"
 
 namespace {
 using namespace cream;
-using TT = Tr<hip_bfloat16>;
-using F = TT::frag;
 
 constexpr float LOG2E = 1.4426950408889634f;
 constexpr int KP = 40;                 // pitch (bf16) of staged row-major [32][32] tiles (rows 8-byte aligned for the transposing read)
@@ -87,18 +85,6 @@ struct Lds {
 };
 struct Geo { const int *tok, *reg, *cyx, *kc; };
 
-__device__ __forceinline__ F scaled(const F x, float s) {
-    f32x8v y;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) y[e] = bf2f(x[e]) * s;
-    return __builtin_bit_cast(F, __builtin_convertvector(y, hwbf16x8));
-}
-__device__ __forceinline__ void store_row32(short* op, const f32x16& o, int g, float mul) {
-#pragma unroll
-    for (int r4 = 0; r4 < 4; ++r4)
-        *reinterpret_cast<u32x2v*>(op + 8 * r4 + 4 * g) =
-            u32x2v{f2bf_pair(o[4 * r4] * mul, o[4 * r4 + 1] * mul), f2bf_pair(o[4 * r4 + 2] * mul, o[4 * r4 + 3] * mul)};
-}
 // tile^T (rows = the 32 tokens of tile t, column = own token) = A rows (global, 32 wide, through the token table) . own^T
 __device__ __forceinline__ f32x16 stream_tile(const short* base, int64_t rs, const int* tok, int t, float a_scale, bool scale_a,
                                               const F (&own)[2], int lane) {
@@ -132,69 +118,6 @@ __device__ __forceinline__ void rows_product(f32x16& acc, const short* tile, con
     for (int s2 = 0; s2 < 2; ++s2) acc = TT::mma(load_perm_tr(tile, KP, 0, s2, lane), TT::from_acc(p, s2), acc);
 }
 
-// ---- the exchange: X[x][r4][lane] (16 bytes each) holds the tile of head hb + x in the accumulator layout ---------------------
-template <int HPW>
-__device__ __forceinline__ void xchg_put(float* X, const f32x16 (&in)[HPW], int hb, int H, int wave, int lane) {
-    __syncthreads();                                   // every wave has read the previous contents
-#pragma unroll
-    for (int s = 0; s < HPW; ++s) {
-        const int x = wave + 4 * s;
-        if (hb + x < H) {
-#pragma unroll
-            for (int r4 = 0; r4 < 4; ++r4)
-                *reinterpret_cast<f32x4v*>(X + ((x * 4 + r4) * 64 + lane) * 4) =
-                    f32x4v{in[s][4 * r4], in[s][4 * r4 + 1], in[s][4 * r4 + 2], in[s][4 * r4 + 3]};
-        }
-    }
-    __syncthreads();
-}
-// out[s] = sum_h W[o_s][h] X[h]  (TRANS: sum_h W[h][o_s] X[h]);  CROSS: cross[h][s] += sum over this lane's 16 elements of
-// own[s] * X[h]  (the lane's share of a weight gradient: row h = the exchanged head, column = the own head of slot s)
-template <int HPW, bool TRANS, bool CROSS>
-__device__ __forceinline__ void xchg_mix(const float* X, f32x16 (&out)[HPW], const float* __restrict__ W, int H, int wave, int lane,
-                                         const f32x16 (&own)[HPW], float (&cross)[4 * HPW][HPW]) {
-#pragma unroll
-    for (int s = 0; s < HPW; ++s) out[s] = f32x16{};
-#pragma unroll
-    for (int h = 0; h < 4 * HPW; ++h) {
-        if (h < H) {
-            f32x16 x;
-#pragma unroll
-            for (int r4 = 0; r4 < 4; ++r4) {
-                const f32x4v v = *reinterpret_cast<const f32x4v*>(X + ((h * 4 + r4) * 64 + lane) * 4);
-                x[4 * r4] = v[0]; x[4 * r4 + 1] = v[1]; x[4 * r4 + 2] = v[2]; x[4 * r4 + 3] = v[3];
-            }
-#pragma unroll
-            for (int s = 0; s < HPW; ++s) {
-                const int o = wave + 4 * s;
-                if (o < H) {
-                    const float w = TRANS ? W[h * H + o] : W[o * H + h];
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) out[s][r] = __builtin_fmaf(w, x[r], out[s][r]);
-                    if constexpr (CROSS) {
-                        float c0 = 0.f, c1 = 0.f;
-#pragma unroll
-                        for (int r = 0; r < 16; r += 2) {
-                            c0 = __builtin_fmaf(own[s][r], x[r], c0);
-                            c1 = __builtin_fmaf(own[s][r + 1], x[r + 1], c1);
-                        }
-                        cross[h][s] += c0 + c1;
-                    }
-                }
-            }
-        }
-    }
-}
-template <int HPW, bool TRANS>
-__device__ __forceinline__ void xchg_mix(const float* X, f32x16 (&out)[HPW], const float* __restrict__ W, int H, int wave, int lane) {
-    float dummy[4 * HPW][HPW];
-    xchg_mix<HPW, TRANS, false>(X, out, W, H, wave, lane, out, dummy);
-}
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
 // the lanes' shares of a weight gradient, summed over the wave in a fixed butterfly, into the workgroup's LDS partial
 // acc[row h][column own head] — lane 0 of the wave that owns the column is the only writer of the entry
 template <int HPW>
@@ -385,7 +308,7 @@ __global__ __launch_bounds__(256) void window_attn_fwd_kernel(const Args a) {
 #pragma unroll
             for (int s = 0; s < HPW; ++s) {
                 const int o = hb + wave + 4 * s;
-                if (o < a.H && qok) store_row32(a.out + (((int64_t)b * a.L + qtok) * a.H + o) * 32, O[s], g, 1.f);
+                if (o < a.H && qok) store_row(a.out + (((int64_t)b * a.L + qtok) * a.H + o) * 32, O[s], g, 1.f);
             }
         }
     }
@@ -581,7 +504,7 @@ __global__ __launch_bounds__(256) void window_attn_bwd_q_kernel(const Args a) {
 #pragma unroll
             for (int s = 0; s < HPW; ++s) {
                 const int h = hb + wave + 4 * s;
-                if (h < a.H && qok) store_row32(a.dq + (int64_t)b * a.dsb + (int64_t)qtok * a.dsn + (int64_t)h * a.dsh, dq[s], g, a.scale);
+                if (h < a.H && qok) store_row(a.dq + (int64_t)b * a.dsb + (int64_t)qtok * a.dsn + (int64_t)h * a.dsh, dq[s], g, a.scale);
             }
         }
     }
@@ -721,8 +644,8 @@ __global__ __launch_bounds__(256) void window_attn_bwd_kv_kernel(const Args a) {
             for (int s = 0; s < HPW; ++s) {
                 const int h = hb + wave + 4 * s;
                 if (h < a.H && kok) {
-                    store_row32(a.dk + (int64_t)b * a.dsb + (int64_t)ktok * a.dsn + (int64_t)h * a.dsh, dk[s], g, 1.f);
-                    store_row32(a.dv + (int64_t)b * a.dsb + (int64_t)ktok * a.dsn + (int64_t)h * a.dsh, dv[s], g, 1.f);
+                    store_row(a.dk + (int64_t)b * a.dsb + (int64_t)ktok * a.dsn + (int64_t)h * a.dsh, dk[s], g, 1.f);
+                    store_row(a.dv + (int64_t)b * a.dsb + (int64_t)ktok * a.dsn + (int64_t)h * a.dsh, dv[s], g, 1.f);
                 }
             }
         }

@@ -122,11 +122,7 @@ def usable(qkv_dtype, device, head_dim, L, rpes, attn_drop_active=False, dropout
 def _desc(qkv, scale, terms, out, lse, sv):
     B, L, _, H, D = qkv.shape
     d = _lib.IrpeAttnDesc()
-    es = qkv.element_size()
-    base = qkv.data_ptr()
-    sb, sn, s3, sh, _ = qkv.stride()
-    d.q, d.k, d.v = base, base + s3 * es, base + 2 * s3 * es
-    d.sb, d.sn, d.sh = sb, sn, sh
+    _lib.set_packed_qkv(d, qkv)
     d.out, d.lse, d.sv = out.data_ptr(), lse.data_ptr(), (sv.data_ptr() if sv is not None else None)
     tq, tk, tv = terms
     nb = 1
@@ -240,10 +236,7 @@ def bwd_core(dout, qkv, out, lse, sv, scale, terms, drop_p=0.0, seed=0, causal=F
     d.dropout_p, d.dropout_seed = float(drop_p), int(seed)
     d.causal = 1 if causal else 0
     d.dout = dout.data_ptr()
-    es = dqkv.element_size()
-    sb, sn, s3, sh, _ = dqkv.stride()
-    d.dq, d.dk, d.dv = dqkv.data_ptr(), dqkv.data_ptr() + s3 * es, dqkv.data_ptr() + 2 * s3 * es
-    d.dsb, d.dsn, d.dsh = sb, sn, sh
+    _lib.set_packed_dqkv(d, dqkv)
     delta = torch.empty((B, H, NP), dtype=torch.float32, device=dev)
     rows = lambda: torch.empty((B, H, NP, 64), dtype=qkv.dtype, device=dev)      # noqa: E731
     lkg = dlk = gg = dlq = None

@@ -66,11 +66,7 @@ def _flops(B, H, L, bwd):
 def _desc(qkv, scale, term, wl, ww, out, lse):
     B, L, _, H, D = qkv.shape
     d = _lib.MiniAttnDesc()
-    es = qkv.element_size()
-    base = qkv.data_ptr()
-    sb, sn, s3, sh, _ = qkv.stride()
-    d.q, d.k, d.v = base, base + s3 * es, base + 2 * s3 * es
-    d.sb, d.sn, d.sh = sb, sn, sh
+    _lib.set_packed_qkv(d, qkv)
     d.out, d.lse = (out.data_ptr() if out is not None else None), lse.data_ptr()
     nb = 1
     if term is not None:
@@ -103,10 +99,7 @@ def bwd_core(dout, qkv, lse, scale, term, wl, ww):
     dqkv = torch.empty_like(qkv, memory_format=torch.contiguous_format)
     d = _desc(qkv, scale, term, wl, ww, None, lse)
     d.dout = dout.data_ptr()
-    es = dqkv.element_size()
-    sb, sn, s3, sh, _ = dqkv.stride()
-    d.dq, d.dk, d.dv = dqkv.data_ptr(), dqkv.data_ptr() + s3 * es, dqkv.data_ptr() + 2 * s3 * es
-    d.dsb, d.dsn, d.dsh = sb, sn, sh
+    _lib.set_packed_dqkv(d, dqkv)
     delta = torch.empty((B, H, NP), dtype=torch.float32, device=dev)
     parts = torch.empty((2, B * (NP // 32), H, H), dtype=torch.float32, device=dev)
     d.delta, d.dwl_part, d.dww_part = delta.data_ptr(), parts[0].data_ptr(), parts[1].data_ptr()

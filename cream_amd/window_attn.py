@@ -75,11 +75,7 @@ def _desc(qkv, scale, table, geometry, mix, out, lse):
     B, L, _, H, D = qkv.shape
     Hs, Ws, w, shift, mask_shift = geometry
     d = _lib.WindowAttnDesc()
-    es = qkv.element_size()
-    base = qkv.data_ptr()
-    sb, sn, s3, sh, _ = qkv.stride()
-    d.q, d.k, d.v = base, base + s3 * es, base + 2 * s3 * es
-    d.sb, d.sn, d.sh = sb, sn, sh
+    _lib.set_packed_qkv(d, qkv)
     d.out, d.lse = (out.data_ptr() if out is not None else None), lse.data_ptr()
     d.table = table.data_ptr()
     if mix is not None:
@@ -118,10 +114,7 @@ def bwd_core(dout, qkv, lse, scale, table, geometry, mix):
     dqkv = torch.empty_like(qkv, memory_format=torch.contiguous_format)
     d = _desc(qkv, scale, table, geometry, mix, None, lse)
     d.dout = dout.data_ptr()
-    es = dqkv.element_size()
-    sb, sn, s3, sh, _ = dqkv.stride()
-    d.dq, d.dk, d.dv = dqkv.data_ptr(), dqkv.data_ptr() + s3 * es, dqkv.data_ptr() + 2 * s3 * es
-    d.dsb, d.dsn, d.dsh = sb, sn, sh
+    _lib.set_packed_dqkv(d, dqkv)
     lib = _lib.load()
     nu = (2 * w - 1) ** 2
     with torch.cuda.device(dev):
