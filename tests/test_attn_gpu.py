@@ -342,3 +342,91 @@ def test_c_abi_dropout_rejects_bad_rates():
     assert lib.cream_attn_rpe2d_fwd_drop(*args(-0.1)) == -1
     assert lib.cream_attn_rpe2d_fwd_drop(*args(float("nan"))) == -1
     torch.cuda.synchronize()
+
+
+# ---- persistent grids smaller than the problem (cream_cu_reserve, the data-parallel driver's CU reserve) ----------------------------
+# (B, H, side, max_rel): more (b, h) items than the 8 workgroups of an 8-CU budget, and no multiple of 8: uneven items per workgroup,
+# the next item's operands travelling under the current item's work, the last item without a successor
+SMALL_GRID = [(5, 2, 7, 14), (3, 3, 15, 14), (11, 1, 5, 3), (3, 3, 14, 14)]
+
+
+class _CuBudget:
+    """`with _CuBudget(8) as lib:` sizes every persistent grid for 8 CUs (None: all of them) and puts the reserve back."""
+
+    def __init__(self, cus):
+        self.cus = cus
+
+    def __enter__(self):
+        from cream_amd import _lib
+        lib = _lib.load()
+        self.lib, self.prev = lib, lib.cream_cu_reserve(0)
+        if self.cus is not None:
+            lib.cream_cu_reserve(lib.cream_cu_count() - self.cus)
+            assert lib.cream_cu_count() == self.cus
+        return lib
+
+    def __exit__(self, *exc):
+        self.lib.cream_cu_reserve(self.prev)
+
+
+def _small_and_full_grid(run, B, H):
+    """run() at the 8-CU budget twice and at the full budget -> (small, full); the rerun reproduces every bit, the table-gradient
+    partials followed the budget (or the Python side sized them for the wrong grid), output and dqkv do not depend on which
+    workgroup ran an item, the table gradients only through the order of the per-workgroup fp32 chains (1e-5)."""
+    with _CuBudget(8) as lib:
+        assert lib.cream_attn_rpe2d_dtab_parts(B, H) == 8 < B * H and (B * H) % 8 != 0
+        small, again = run(), run()
+    with _CuBudget(None) as lib:
+        assert lib.cream_attn_rpe2d_dtab_parts(B, H) == B * H
+        full = run()
+    assert torch.equal(small[0], again[0]) and all(torch.equal(a, b) for a, b in zip(small[1], again[1]))
+    assert torch.isfinite(small[0]).all() and all(torch.isfinite(t).all() for t in small[1])
+    assert torch.equal(small[0], full[0]) and torch.equal(small[1][0], full[1][0])
+    for a, b in zip(small[1][1:], full[1][1:]):
+        assert _rel(a, b) < 1e-5
+    return small, full
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("B,H,side,mr", SMALL_GRID)
+def test_fused_attention_on_a_grid_smaller_than_the_items(B, H, side, mr, dtype):
+    """Every instantiation (fp32, bf16; the AutoFormer geometry, the generic ones) with several items per workgroup:
+    oracle parity at the documented tolerances, and the same bits as on the full grid."""
+    qkv, tabs, go = _inputs(B, H, side, mr, seed=7)
+    ref_out, ref_g = _oracle(qkv, tabs, go, mr)
+    (out, g), _ = _small_and_full_grid(lambda: _fused(qkv, tabs, go, mr, dtype), B, H)
+    assert _rel(out, ref_out) < (1e-3 if dtype == torch.float32 else 2e-2)
+    for a, b in zip(g, ref_g):
+        assert _rel(a, b) < (1e-3 if dtype == torch.float32 else 3e-2)
+
+
+@pytest.mark.parametrize("fwd_mode", [0, 1])
+@pytest.mark.parametrize("bwd_mode", [0, 1, 2])
+def test_kernel_variants_of_the_benchmark_geometry_on_a_grid_smaller_than_the_items(bwd_mode, fwd_mode):
+    """N = 197 in bf16: both forward kernels and the three backward implementations walk several items per workgroup."""
+    from cream_amd import _lib
+    lib = _lib.load()
+    B, H, side, mr = 3, 3, 14, 14
+    qkv, tabs, go = _inputs(B, H, side, mr, seed=8)
+    ref_out, ref_g = _oracle(qkv, tabs, go, mr)
+    prev_b, prev_f = lib.cream_attn_rpe2d_bwd_mode(-1), lib.cream_attn_rpe2d_fwd_mode(-1)
+    try:
+        lib.cream_attn_rpe2d_bwd_mode(bwd_mode)
+        lib.cream_attn_rpe2d_fwd_mode(fwd_mode)
+        (out, g), _ = _small_and_full_grid(lambda: _fused(qkv, tabs, go, mr, torch.bfloat16), B, H)
+    finally:
+        lib.cream_attn_rpe2d_bwd_mode(prev_b)
+        lib.cream_attn_rpe2d_fwd_mode(prev_f)
+    assert _rel(out, ref_out) < 2e-2
+    for a, b in zip(g, ref_g):
+        assert _rel(a, b) < 3e-2
+
+
+def test_fused_attention_dropout_on_a_grid_smaller_than_the_items():
+    B, H, side, mr, p, seed = 5, 2, 7, 14, 0.1, 4321
+    qkv, tabs, go = _inputs(B, H, side, mr, seed=9)
+    ref_out, ref_g = _oracle_drop(qkv, tabs, go, mr, _keep(seed, p, B, H, side * side + 1))
+    (out, g), _ = _small_and_full_grid(lambda: _fused_drop(qkv, tabs, go, mr, torch.float32, p, seed), B, H)
+    assert _rel(out, ref_out) < 1e-3
+    for a, b in zip(g, ref_g):
+        assert _rel(a, b) < 1e-3

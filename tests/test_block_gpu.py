@@ -752,6 +752,55 @@ def test_bf16_partial_tiles_of_the_weight_gradients_stay_within_their_rounding()
     assert 0.0 < worst < 4e-3
 
 
+def test_block_under_the_multi_gpu_cu_reserve_equals_the_full_grid():
+    """cream_cu_reserve(comm.DEFAULT_COMM_CUS) — what every multi-GPU run sets — against reserve 0 on the small two-block model:
+    the persistent grids shrink and the token slices of the weight gradients (= the backward workspace layout, cream_block_layout_epoch)
+    change.  Per-element arithmetic does not depend on the grid: outputs, dx and every gradient that is no split-K weight gradient are
+    bit-identical; the four weight gradients per block differ by the rounding of other partial tiles (the 4e-3 of
+    test_bf16_partial_tiles_of_the_weight_gradients_stay_within_their_rounding).  The qkv bias gradient is split-K too: its fp32 partials
+    (column sums of dqkv per token slice) ride on the qkv weight-gradient kernel (csrc/block_seq.cpp), so other slices add the same terms
+    in another order — the 1e-5 of test_block_stack_equals_block_by_block_with_drop_path for summation-order noise.  A workspace laid out
+    for the other budget would show here."""
+    from cream_amd import _lib, comm
+    from cream_amd.autoformer import block as K
+    lib = _lib.load()
+    m = _supernet().to(DEV)
+    m.set_sample_config(dict(layer_num=2, embed_dim=[384, 384], num_heads=[6, 5], mlp_ratio=[3.5, 3.0]))
+    m.train()
+    g = torch.Generator(device=DEV).manual_seed(13)
+    B = 8
+    x0 = torch.randn(B, 197, 384, device=DEV, generator=g)
+    dout = torch.randn(B, 197, 384, device=DEV, generator=g)
+    blks = list(m.blocks)
+    res, splits = [], []
+    prev = lib.cream_cu_reserve(-1)
+    try:
+        for reserve in (0, comm.DEFAULT_COMM_CUS, 0):
+            lib.cream_cu_reserve(reserve)
+            splits.append(K._wgrad_splits(B * 197, 3 * 320, 384, False, K.wgrad_parts_dtype()))      # block 1's qkv weight gradient
+            m.zero_grad(set_to_none=True)
+            x = x0.clone().requires_grad_()
+            y = K.StackFunction.apply(x, None, blks)
+            y.backward(dout)
+            torch.cuda.synchronize()
+            res.append((y.detach().clone(), x.grad.clone(), {k: p.grad.clone() for k, p in m.named_parameters() if p.grad is not None}))
+    finally:
+        lib.cream_cu_reserve(prev)
+    assert splits[0] != splits[1], "the token slices did not follow the budget: the case tests nothing"
+    big = ("attn.qkv.weight", "attn.proj.weight", "fc1.weight", "fc2.weight")
+    for other in (1, 2):                                           # reserve 16, and back at 0 (the epoch moved twice)
+        assert torch.equal(res[0][0], res[other][0]) and torch.equal(res[0][1], res[other][1])
+        assert set(res[0][2]) == set(res[other][2]) and len(res[0][2]) >= 2 * 16
+        for k, v in res[0][2].items():
+            assert torch.isfinite(res[other][2][k]).all(), k
+            if other == 1 and k.endswith(big):
+                assert _rel(res[other][2][k], v) < 4e-3, k
+            elif other == 1 and k.endswith("attn.qkv.bias"):
+                assert _rel(res[other][2][k], v) < 1e-5, k
+            else:
+                assert torch.equal(res[other][2][k], v), k
+
+
 @pytest.mark.parametrize("B,C,dt", [(128, 1000, torch.bfloat16), (5, 1000, torch.float32), (16, 2048, torch.bfloat16), (3, 37, torch.float32)])
 def test_soft_target_ce_kernel_matches_torch(B, C, dt):
     """cream_soft_ce (loss rows + logit gradient in one launch) against the framework formulation of
