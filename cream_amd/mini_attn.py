@@ -90,8 +90,9 @@ def fwd_core(qkv, scale, term, wl, ww):
     return out, lse
 
 
-def bwd_core(dout, qkv, lse, scale, term, wl, ww):
-    """The backward launches of fwd_core: -> (dqkv (B, L, 3, H, 64) bf16, d table or None, d wl, d ww).  Outside autograd."""
+def bwd_core(dout, qkv, lse, scale, term, wl, ww, *, return_delta=False):
+    """The backward launches of fwd_core: -> (dqkv (B, L, 3, H, 64) bf16, d table or None, d wl, d ww).  Outside autograd.
+    `return_delta`: also the (B, H, NP) fp32 delta rows of the first launch (for the kernel tests)."""
     B, L, _, H, D = qkv.shape
     NP = padded_len(L)
     dev = qkv.device
@@ -126,7 +127,8 @@ def bwd_core(dout, qkv, lse, scale, term, wl, ww):
                 g = g.sum(0, keepdim=True)
             dtab = g[:, :, :nb].to(w.dtype).contiguous()
     dw = parts.sum(1)                               # fixed order: (2, H, H)
-    return dqkv, dtab, dw[0].reshape(wl.shape).contiguous(), dw[1].reshape(ww.shape).contiguous()
+    res = (dqkv, dtab, dw[0].reshape(wl.shape).contiguous(), dw[1].reshape(ww.shape).contiguous())
+    return res + (delta,) if return_delta else res
 
 
 class _Mixed(torch.autograd.Function):

@@ -104,9 +104,10 @@ def fwd_core(qkv, scale, table, geometry, mix):
     return out, lse
 
 
-def bwd_core(dout, qkv, lse, scale, table, geometry, mix):
+def bwd_core(dout, qkv, lse, scale, table, geometry, mix, *, return_delta=False):
     """The two backward launches of fwd_core: -> (dqkv (B, Hs*Ws, 3, H, 32) bf16, d table, (d wl, d bl, d ww, d bw) or
-    None).  Outside autograd."""
+    None).  Outside autograd.  `return_delta`: also the (B*nW, H, 64) fp32 delta rows the query launch hands to the key
+    launch (for the kernel tests)."""
     B, L, _, H, D = qkv.shape
     w = geometry[2]
     dev = qkv.device
@@ -135,6 +136,8 @@ def bwd_core(dout, qkv, lse, scale, table, geometry, mix):
         o = nu * H
         dmix = (p[o:o + H * H].reshape(H, H), p[o + 2 * H * H:o + 2 * H * H + H],
                 p[o + H * H:o + 2 * H * H].reshape(H, H), p[o + 2 * H * H + H:o + 2 * H * H + 2 * H])
+    if return_delta:
+        return dqkv, dtab, dmix, delta
     return dqkv, dtab, dmix
 
 

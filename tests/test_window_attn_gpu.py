@@ -104,6 +104,10 @@ CASES = {
     "one_head": dict(H=1, res=(14, 14), shift=3, mix=True, B=1),              # 1 x 1 mixes
     # 640 work items: more than the persistent grids have workgroups, so a workgroup loops over items and its partial sums them
     "many_items": dict(H=2, res=(14, 14), shift=3, mix=True, B=80),
+    # other window sizes through the module: one key tile (w = 4), 64 keys without padding (w = 8); 12 heads = three head slots
+    "window4": dict(H=3, res=(8, 12), shift=2, mix=True, B=2, window=4),
+    "window8": dict(H=3, res=(16, 24), shift=4, mix=True, B=2, window=8),
+    "mixed_12": dict(H=12, res=(14, 14), shift=3, mix=True, B=2),
 }
 
 
@@ -122,7 +126,8 @@ def case_inputs(c, seed=5):
     return x, gy
 
 
-def make_layer(c, window=7, **kw):
+def make_layer(c, window=None, **kw):
+    window = window or c.get("window", 7)
     m = Layer(c["H"], c["res"], window, c["shift"], c["mix"], **kw).to(DEV)
     if c["shift"] == 0 and m.blk.shift_size > 0:
         # an unshifted, unmasked layer (plain Swin's even blocks): the reference's shared block would still pass its mask
