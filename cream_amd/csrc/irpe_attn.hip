@@ -24,11 +24,11 @@
 // converted once per (table, device) to padded uint8 matrices in BOTH orientations (query-major for the
 // kernels whose lanes own queries, key-major for the dK/dV kernel), every 32-byte group in lane order
 // (bucket_bytes_kernel), 370 KB at L=577: L2 resident.  Scatter-adds (value-side bucket sums, bucket gradients) are
-// LDS float atomics into rows owned by the wave.
+// ordered read-modify-writes into rows owned by the wave (scatter_add16, attn_lane.hpp), not LDS float atomics.
 //
-// Forward softmax is two-pass (max first, then exp / sums / P.V): the bucket sums cannot be rescaled
-// cheaply when a running maximum moves, and the second pass is exactly what backward needs anyway
-// (P from the saved log-sum-exp).  K is streamed twice through LDS (L2 hits), V once.
+// Forward softmax is one pass with a LAZY running maximum (it moves only when a tile exceeds it by more than 8):
+// rescaling o, l and the bucket sums is then a rare wave-uniform branch.  Backward recomputes P from the saved
+// log-sum-exp.  K and V are streamed once through LDS.
 //
 // Backward, with G = dO Wv^T (the value-side lookups of dO) and delta_i = dO_i . O_i:
 //     dP[i,j] = dO_i . v_j + G[i, idv[i,j]]        dS = P o (dP - delta)
@@ -744,10 +744,9 @@ __global__ __launch_bounds__(256) void irpe_attn_bwd_kv_kernel(const Args a) {  
         __syncthreads();
         if (active) {
             if (a.wq) {
-                F ksf[4];
-#pragma unroll
-                for (int ks = 0; ks < 4; ++ks) ksf[ks] = scaled(kf[ks], a.scale);
-                lookups_to_lds<LBP>(lqw, tab0, ksf, 1.f, lane);               // (k * scale) Wq (:82)
+                // (k Wq) * scale: product first, scale after, rounded once — bit for bit the rows lq_tile (forward) and
+                // irpe_lq_rows_kernel (launch A) use, also for a scale that is no power of two (bf16(k * scale) Wq is not)
+                lookups_to_lds<LBP>(lqw, tab0, kf, a.scale, lane);
             } else {
                 bias_rows_to_lds<LBP>(lqw, a.bq + (int64_t)h * a.bq_hs, a.nb, lane);
             }

@@ -714,10 +714,9 @@ __global__ __launch_bounds__(256) void irpe_x_bwd_kv_kernel(const Args a) {
         __syncthreads();
         if (active) {
             if (a.wq) {
-                F ksf[KS];
-#pragma unroll
-                for (int ks = 0; ks < KS; ++ks) ksf[ks] = scaled(kf[ks], a.scale);
-                lookups_to_lds<G>(lqw, tab0, ksf, 1.f, lane);               // (k * scale) Wq
+                // (k Wq) * scale: product first, scale after, rounded once — bit for bit the rows lq_tile (forward) and
+                // irpe_x_lq_rows_kernel (launch A) use, also for a scale that is no power of two (bf16(k * scale) Wq is not)
+                lookups_to_lds<G>(lqw, tab0, kf, a.scale, lane);
             } else {
                 bias_rows_to_lds<G>(lqw, a.bq + (int64_t)h * a.bq_hs, a.nb, lane);
             }

@@ -221,9 +221,11 @@ def fwd_core(qkv, scale, terms, drop_p=0.0, seed=0, causal=False):
     return out, lse, sv
 
 
-def bwd_core(dout, qkv, out, lse, sv, scale, terms, drop_p=0.0, seed=0, causal=False):
+def bwd_core(dout, qkv, out, lse, sv, scale, terms, drop_p=0.0, seed=0, causal=False, *, return_rows=False):
     """The backward launches of fwd_core: -> (dqkv (B, L, 3, H, 64), [d table of rpe_q, rpe_k, rpe_v] — each None or a tensor of the
-    table's shape and dtype).  Outside autograd."""
+    table's shape and dtype).  Outside autograd.  `return_rows`: also a dict of what the launches hand to each other — `delta`
+    (B, H, NP) fp32 and the bf16 side rows `lkg`, `gg`, `dlk`, `dlq` (B, H, NP, 64), None where the term is absent (for the
+    kernel tests)."""
     tq, tk, tv = terms
     if tv is None:
         sv = None
@@ -291,6 +293,8 @@ def bwd_core(dout, qkv, out, lse, sv, scale, terms, drop_p=0.0, seed=0, causal=F
             res.append(gpart[:, :nb].to(w.dtype).contiguous())
             continue
         res.append((gpart[:, :, :nb] if transposed else gpart[:, :nb, :]).to(w.dtype).contiguous())
+    if return_rows:
+        return dqkv, res, dict(delta=delta, lkg=lkg, gg=gg, dlk=dlk, dlq=dlq)
     return dqkv, res
 
 
@@ -412,10 +416,12 @@ def fwd_core_x(q, k, v, scale, terms, key_pad=None, drop_p=0.0, seed=0, causal=F
 
 
 def bwd_core_x(dout, q, k, v, out, lse, sv, scale, terms, key_pad=None, drop_p=0.0, seed=0, causal=False, seq_first=False,
-               partials=None):
+               partials=None, *, return_rows=False):
     """The backward launches of fwd_core_x: -> ((dq, dk, dv) as (B, L, H, D) views of one buffer laid out like `out`,
     [d table of rpe_q, rpe_k, rpe_v]).  `partials`: a dict that receives the per-image table-gradient partials
-    (B, H, ., .) before their reduction over the batch (tests).  Outside autograd."""
+    (B, H, ., .) before their reduction over the batch (tests).  Outside autograd.  `return_rows`: also a dict of `delta`
+    (B, H, NP) fp32 and the bf16 side rows `lkg`, `gg`, `dlk`, `dlq` (B, H, NP, row width), None where the term is absent
+    (for the kernel tests)."""
     tq, tk, tv = terms
     if tv is None:
         sv = None
@@ -496,6 +502,8 @@ def bwd_core_x(dout, q, k, v, out, lse, sv, scale, terms, key_pad=None, drop_p=0
             res.append(gpart[:, :nb].to(w.dtype).contiguous())
             continue
         res.append((gpart[:, :, :nb] if transposed else gpart[:, :nb, :]).to(w.dtype).contiguous())
+    if return_rows:
+        return (dq, dk, dv), res, dict(delta=delta, lkg=lkg, gg=gg, dlk=dlk, dlq=dlq)
     return (dq, dk, dv), res
 
 
