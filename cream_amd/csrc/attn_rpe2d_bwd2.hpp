@@ -1,7 +1,6 @@
 // attn_rpe2d_bwd2.hpp — the one-pass attention backward with the two roles of attn_rpe2d_bwd1.hpp on SEPARATE waves
-// (round 6; AutoFormer geometry N = 197, 14 x 14 grid, max_relative_position 14, bf16).  Included by attn_rpe2d.hip behind
-// attn_rpe2d_bwd1.hpp (same LDS layout, same helpers: namespace v2); reference semantics:
-// AutoFormer/model/module/multihead_super.py:133-160, SURVEY App. B.
+// (round 6; AutoFormer geometry N = 197, 14 x 14 grid, max_relative_position 14, bf16).  Same LDS layout and helpers as
+// bwd1: attn_rpe2d_whole14.hpp; reference semantics: AutoFormer/model/module/multihead_super.py:133-160, SURVEY App. B.
 //
 // Why.  In bwd1 every one of the 7 waves is owner of a query tile AND owner of a key tile: 112 accumulator registers of
 // gradients + 32 of scores pin 238 VGPRs, so a CU holds 7 waves (2 + 2 + 2 + 1 on its SIMDs) and every phase of an item
@@ -37,6 +36,7 @@
 //        4        4  9                          6 7                3
 // LDS as in bwd1 (K | V | Q | dO | one-hot rows | 7 exchange slots = 161,280 B).
 #pragma once
+#include "attn_rpe2d_whole14.hpp"
 
 // timing experiments of tools/probes/attn_bwd1_probe.hip (results are WRONG with either switch): leave out the global row
 // stores of dq / dk / dv, or the loads of the next item's matrices and O rows (the LDS keeps the first item's)
@@ -49,29 +49,23 @@
 
 // phase stamps for tools/probes/attn_bwd1_probe.hip (compiled out of the library): 12 slots per wave, 12 waves per workgroup
 #ifdef ATTN_PROFILE
-#define V4_PROF_DECL long long pt4[12]; int pn4 = 0;
-#define V4_MARK() do { pt4[pn4++] = (long long)__builtin_readcyclecounter(); } while (0)
-#define V4_FLUSH() do { if ((threadIdx.x & 63) == 0 && g_attn_prof) { \
+#define BWD2_PROF_DECL long long pt4[12]; int pn4 = 0;
+#define BWD2_MARK() do { pt4[pn4++] = (long long)__builtin_readcyclecounter(); } while (0)
+#define BWD2_FLUSH() do { if ((threadIdx.x & 63) == 0 && g_attn_prof) { \
         long long* d_ = g_attn_prof + ((long long)blockIdx.x * 12 + (threadIdx.x >> 6)) * 12; \
         for (int i_ = 0; i_ < 12; ++i_) d_[i_] = i_ < pn4 ? pt4[i_] : 0; } } while (0)
 #else
-#define V4_PROF_DECL
-#define V4_MARK() do {} while (0)
-#define V4_FLUSH() do {} while (0)
+#define BWD2_PROF_DECL
+#define BWD2_MARK() do {} while (0)
+#define BWD2_FLUSH() do {} while (0)
 #endif
 
-namespace v4 {
+namespace {
+namespace bwd2 {
+using namespace whole14;
 
-using v2::NT; using v2::N14; using v2::NP14; using v2::MAT_B;
-using v2::OFF_K; using v2::OFF_V; using v2::OFF_Q; using v2::OFF_D; using v2::OFF_OH; using v2::OFF_X;
-using v2::SLOT_B; using v2::XT_B; using v2::SCRP;
-using v2::IMG_KR; using v2::IMG_KT; using v2::IMG_VR;
-using v2::LaneOffs; using v2::lane_offs; using v2::swz128; using v2::tr_pair; using v2::lds_b128; using v2::mma16;
-using v2::lds_barrier; using v2::dma_1k; using v2::dma_wait_all; using v2::ext_from_lookups14;
-using v2::slots_to_buckets14_bf16; using v2::store_tile_staged;
-
-constexpr int NPROD = 7, NCONS = 5, WAVES = NPROD + NCONS, THREADS = WAVES * 64;
-constexpr int LDS_B = v2::OFF_SINK;                  // (no prefetch sink)
+constexpr int NPROD = 7, NCONS = 5, WAVES = NPROD + NCONS, THREADS = WAVES * 64;    // (THREADS, LDS_B: this kernel's, not whole14's)
+constexpr int LDS_B = OFF_SINK;                      // (no prefetch sink)
 constexpr int JOBS = 3;                              // key-side jobs per consumer (14 over 5: 3 3 3 3 2)
 static_assert(LDS_B <= 160 * 1024, "LDS budget");
 
@@ -82,7 +76,7 @@ __device__ __forceinline__ void mat_dma12(const short* src, int64_t rs, uint32_t
         const int piece = wave + WAVES * i;
         if (piece < 28) {                            // (wave-uniform)
             const int row = piece * 8 + (lane >> 3), cc = lane & 7;
-            const short* s = row < N14 ? src + (int64_t)row * rs + ((cc ^ swz128(row)) << 3) : reinterpret_cast<const short*>(v2::g_zero_line);
+            const short* s = row < N14 ? src + (int64_t)row * rs + ((cc ^ swz128(row)) << 3) : reinterpret_cast<const short*>(g_zero_line);
             dma_1k(s, lds_base + piece * 1024);
         }
     }
@@ -92,7 +86,7 @@ __device__ __forceinline__ void fill_onehot12(unsigned char* oh) {
     const RelGeom G{N14, G14, G14, G14};
     for (int i = threadIdx.x; i < NP14 * 4; i += THREADS) {
         const int j = i >> 2, cc = i & 3;
-        const uint32_t m = (key_mask(j, G) | (j >= N14 ? 1u << 15 : 0u)) >> (8 * cc);     // (slot 15: padding keys, see v2::fill_onehot_swz)
+        const uint32_t m = (key_mask(j, G) | (j >= N14 ? 1u << 15 : 0u)) >> (8 * cc);     // (slot 15: padding keys, see whole14::fill_onehot_swz)
         u32x4v w;
 #pragma unroll
         for (int p = 0; p < 4; ++p) w[p] = ((m >> (2 * p)) & 1u) * 0x3F80u + ((m >> (2 * p + 1)) & 1u) * 0x3F800000u;
@@ -151,7 +145,7 @@ __device__ __forceinline__ void producer_items(const BwdArgs& a, const short* im
         lse_r = a.lse[I.bh * N14 + qcl0];
     }
     for (;;) {
-        // (thread-derived values from an OPAQUE copy per item: see v2 — no address of the loop body is hoisted across items)
+        // (thread-derived values from an OPAQUE copy per item: see bwd1 — no address of the loop body is hoisted across items)
         int tid = threadIdx.x;
         asm volatile("" : "+v"(tid));
         const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -163,8 +157,8 @@ __device__ __forceinline__ void producer_items(const BwdArgs& a, const short* im
         const bool more = next < a.nitems;
         Item In = I;
         if (more) In = item_of(a, next);
-        V4_PROF_DECL
-        V4_MARK();                                   // 0: item start
+        BWD2_PROF_DECL
+        BWD2_MARK();                                   // 0: item start
         const int qi = wave * 32 + c32;
         const bool tok_ok = qi < N14;
         const int qcl = min(qi, N14 - 1);
@@ -182,7 +176,7 @@ __device__ __forceinline__ void producer_items(const BwdArgs& a, const short* im
             for (int t = 0; t < 2; ++t) tv[t][ks] = *reinterpret_cast<const bf16x8*>(img + IMG_VR + (32 * t + c32) * 64 + ks * 16 + g * 8);
         dma_wait_all();                              // this wave's pieces of K, V, Q, dO have landed ...
         lds_barrier();                               // ... and everybody's                                    [top]
-        V4_MARK();                                   // 1: operands landed
+        BWD2_MARK();                                   // 1: operands landed
         const float m2 = tok_ok ? lse_r * LOG2E : INFINITY;
         bf16x8 qe[2], de[2];
         float dsc;
@@ -217,7 +211,7 @@ __device__ __forceinline__ void producer_items(const BwdArgs& a, const short* im
         }
 
         f32x16 dq[2] = {f32x16{}, f32x16{}}, dx = {};
-        V4_MARK();                                   // 2: prologue done
+        BWD2_MARK();                                   // 2: prologue done
 #pragma unroll 1
         for (int s = 0; s < NT; ++s) {
             const int j = wave + s < NT ? wave + s : wave + s - NT;             // this step's key tile (wave-uniform)
@@ -273,7 +267,7 @@ __device__ __forceinline__ void producer_items(const BwdArgs& a, const short* im
             }
             lds_barrier();                           // [B] the tiles of step s are in place
         }
-        V4_MARK();                                   // 3: steps done
+        BWD2_MARK();                                   // 3: steps done
         // K and V are dead.  Every region of the next item is requested as soon as its last reader is through: K now, dO behind
         // [C] (the consumers stage their rows through the V region), V behind [D], Q behind [E]
         if (more && !BWD2_EXP_NOLOAD) mat_dma12(In.kpg, a.sn, lds0 + OFF_K, wave, lane);
@@ -289,8 +283,8 @@ __device__ __forceinline__ void producer_items(const BwdArgs& a, const short* im
 #pragma unroll
             for (int dt = 0; dt < 2; ++dt) ktf[ks][dt] = *reinterpret_cast<const bf16x8*>(img + IMG_KT + (c32 + 32 * dt) * 64 + g * 32 + ks * 8);
         lds_barrier();                               // [C] the consumers are through with the last tiles: the slots are free
-        V4_MARK();                                   // 4: behind [C]
-        if (more && !BWD2_EXP_NOLOAD) v2::mat_dma(In.dop, orow, lds0 + OFF_D, wave, lane);         // (7 waves x 4 pieces)
+        BWD2_MARK();                                   // 4: behind [C]
+        if (more && !BWD2_EXP_NOLOAD) mat_dma(In.dop, orow, lds0 + OFF_D, wave, lane);         // (7 waves x 4 pieces)
         const int64_t goff = (int64_t)b * a.dsb + (int64_t)(wave * 32) * a.dsn + (int64_t)h * a.dsh;
         {
             bf16x8 bk[4];
@@ -309,14 +303,14 @@ __device__ __forceinline__ void producer_items(const BwdArgs& a, const short* im
                 *reinterpret_cast<u32x4v*>(myslot + c32 * 128 + (((4 * g + ks) ^ swz128(c32)) << 4)) = u.v;
             }
         }
-        V4_MARK();                                   // 5: epilogue done
+        BWD2_MARK();                                   // 5: epilogue done
         lds_barrier();                               // [D] all dL' tiles are in place
-        V4_MARK();                                   // 6: behind [D]
+        BWD2_MARK();                                   // 6: behind [D]
         if (more && !BWD2_EXP_NOLOAD) mat_dma12(In.vpg, a.sn, lds0 + OFF_V, wave, lane);
         lds_barrier();                               // [E] the key-table jobs are done with Q and the slots
-        V4_MARK();                                   // 7: behind [E]
+        BWD2_MARK();                                   // 7: behind [E]
 #ifdef ATTN_PROFILE
-        if (item == (int)(blockIdx.x + gridDim.x)) V4_FLUSH();                  // the SECOND item: one with a predecessor and a successor
+        if (item == (int)(blockIdx.x + gridDim.x)) BWD2_FLUSH();                  // the SECOND item: one with a predecessor and a successor
 #endif
         if (!more) break;
         // Q of the next item (its last readers are behind [E])
@@ -356,15 +350,15 @@ __device__ __forceinline__ void consumer_items(const BwdArgs& a, unsigned char* 
         const bool more = next < a.nitems;
         Item In = I;
         if (more) In = item_of(a, next);
-        V4_PROF_DECL
-        V4_MARK();                                   // 0: item start
+        BWD2_PROF_DECL
+        BWD2_MARK();                                   // 0: item start
         // value-table jobs: S'^T row fragments of query tile t (bucket c32 of table `tab & 1`), one tile ahead (tile 0: an item ahead)
         const short* spr[NV > 0 ? NV : 1];
 #pragma unroll
         for (int v = 0; v < NV; ++v) spr[v] = reinterpret_cast<const short*>(a.sp) + (bh * 64 + (((vj0 + v) >> 1) & 1) * 32 + c32) * NP14;
         dma_wait_all();
         lds_barrier();                               //                                                          [top]
-        V4_MARK();                                   // 1
+        BWD2_MARK();                                   // 1
         f32x16 acc[KJ][2];
 #pragma unroll
         for (int jb = 0; jb < KJ; ++jb) { acc[jb][0] = f32x16{}; acc[jb][1] = f32x16{}; }
@@ -386,7 +380,7 @@ __device__ __forceinline__ void consumer_items(const BwdArgs& a, unsigned char* 
                 }
             }
         };
-        V4_MARK();                                   // 2
+        BWD2_MARK();                                   // 2
 #pragma unroll 1
         for (int s = 0; s < NT; ++s) {
             if (s > 0) consume(s - 1);
@@ -406,11 +400,11 @@ __device__ __forceinline__ void consumer_items(const BwdArgs& a, unsigned char* 
             lds_barrier();                           // [A]
             lds_barrier();                           // [B]
         }
-        V4_MARK();                                   // 3: steps done
+        BWD2_MARK();                                   // 3: steps done
         if (more && !BWD2_EXP_NOLOAD) mat_dma12(In.kpg, a.sn, lds0 + OFF_K, wave, lane);
         consume(NT - 1);
         lds_barrier();                               // [C] (V is dead since step 6: its region stages the rows)
-        V4_MARK();                                   // 4: behind [C]
+        BWD2_MARK();                                   // 4: behind [C]
         unsigned char* stage = smem + OFF_V + c * 4096;
 #pragma unroll
         for (int jb = 0; jb < KJ; ++jb) {
@@ -420,9 +414,9 @@ __device__ __forceinline__ void consumer_items(const BwdArgs& a, unsigned char* 
             if (!BWD2_EXP_NOSTORE) store_tile_staged(stage, reinterpret_cast<short*>(t ? a.dk : a.dv) + goff, a.dsn, j * 32, acc[jb], lane);
             else { asm volatile("" :: "v"(acc[jb][0]), "v"(acc[jb][1])); }
         }
-        V4_MARK();                                   // 5: rows out
+        BWD2_MARK();                                   // 5: rows out
         lds_barrier();                               // [D]
-        V4_MARK();                                   // 6: behind [D]
+        BWD2_MARK();                                   // 6: behind [D]
         if (more && !BWD2_EXP_NOLOAD) mat_dma12(In.vpg, a.sn, lds0 + OFF_V, wave, lane);
         if (more) {
 #pragma unroll
@@ -449,9 +443,9 @@ __device__ __forceinline__ void consumer_items(const BwdArgs& a, unsigned char* 
                 }
         }
         lds_barrier();                               // [E]
-        V4_MARK();                                   // 7: behind [E]
+        BWD2_MARK();                                   // 7: behind [E]
 #ifdef ATTN_PROFILE
-        if (item == (int)(blockIdx.x + gridDim.x)) V4_FLUSH();
+        if (item == (int)(blockIdx.x + gridDim.x)) BWD2_FLUSH();
 #endif
         if (!more) break;
         if (!BWD2_EXP_NOLOAD) mat_dma12(In.qp, a.sn, lds0 + OFF_Q, wave, lane);
@@ -493,4 +487,5 @@ __global__ __launch_bounds__(THREADS) void attn_rpe2d_bwd2_kernel(const BwdArgs 
     else consumer_items<2, 2, 1>(a, smem, lds0, item, I, 4, 6, 3);
 }
 
-}  // namespace v4
+}  // namespace bwd2
+}  // namespace

@@ -1,7 +1,7 @@
 // attn_rpe2d_fwd2.hpp — forward of the fused attention for the AutoFormer geometry (N = 197, 14 x 14 grid,
 // max_relative_position 14, bf16) with TILE-GRANULAR online softmax and two half-workgroups in PING-PONG.
-// Included by attn_rpe2d.hip inside its anonymous namespace, after attn_rpe2d_bwd1.hpp (shares its primitives: DMA,
-// swizzles, transposing LDS reads, the bf16 slot <-> bucket shifts, the staged row store).
+// Primitives shared with the one-pass backward kernels (DMA, swizzles, transposing LDS reads, the bf16 slot <-> bucket
+// shifts, the staged row store): attn_rpe2d_whole14.hpp.
 // Reference semantics: AutoFormer/model/module/multihead_super.py:133-154.
 //
 // Why.  attn_rpe2d_fwd14 keeps the whole row block of scores of a query tile in registers (7 tiles x 16 = 112 VGPRs; 256
@@ -33,6 +33,7 @@
 //                                    element-wise phase (the halves alternate, one barrier between them)
 // The bucket tables are read from the bf16 operand images (table_images_kernel / cream_attn_rpe2d_table_images).
 #pragma once
+#include "attn_rpe2d_whole14.hpp"
 
 #ifdef ATTN_PROFILE
 #define F2_PROF_DECL long long f2t[16]; int f2n = 0;
@@ -46,8 +47,9 @@
 #define F2_FLUSH() do {} while (0)
 #endif
 
-namespace v3 {
-using namespace v2;
+namespace {
+namespace fwd2 {
+using namespace whole14;
 
 constexpr int F2_THREADS = 2 * THREADS;                 // 14 waves
 constexpr int F2_OFF_OH = 4 * MAT_B;
@@ -325,4 +327,5 @@ __global__ __launch_bounds__(F2_THREADS) void attn_rpe2d_fwd2_kernel(const FwdAr
     for (; phase < nk + 2; ++phase) lds_barrier();
 }
 
-}  // namespace v3
+}  // namespace fwd2
+}  // namespace

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "cream_amd.h"
+#include "env_switch.hpp"
 
 namespace {
 
@@ -201,16 +202,9 @@ enum ProfKind { K_LN_FWD = 0, K_GEMM_NT, K_GEMM_NT_GELU, K_GEMM_NT_MUL, K_GEMM_T
 const char* const kProfNames[K_COUNT] = {"ln_fwd", "gemm_nt", "gemm_nt_gelu", "gemm_nt_mul", "gemm_tn_wgrad", "attn_rpe2d_fwd",
                                          "attn_rpe2d_bwd", "ln_bwd", "grad_finalize"};
 // split-K partial tiles of the weight gradients as bf16 (cream_linear_wgrad_parts_bf16): half the partial traffic
-std::atomic<int> g_wgrad_bf16{-1};
-int wgrad_bf16_mode() {
-    int m = g_wgrad_bf16.load(std::memory_order_relaxed);
-    if (m < 0) {
-        const char* e = getenv("CREAM_WGRAD_BF16");
-        m = e ? (atoi(e) != 0) : 1;              // default ON: -2 % step time in a same-box A/B x3 (profiles/r04_step_ab.md)
-        g_wgrad_bf16.store(m, std::memory_order_relaxed);
-    }
-    return m;
-}
+// default ON: -2 % step time in a same-box A/B x3 (profiles/r04_step_ab.md)
+cream::EnvSwitch g_wgrad_bf16{"CREAM_WGRAD_BF16", 1, cream::norm_bool};
+int wgrad_bf16_mode() { return g_wgrad_bf16.get(); }
 
 // the split-K weight-gradient launch in either partial format (the workspace regions are sized for fp32)
 int wgrad_parts(int bf16, float* parts, float* bias_parts, const void* dy, const void* x, int M, int N, int K, int S, void* stream) {
@@ -430,13 +424,7 @@ int cream_block_bwd(const cream_block_desc* d, const cream_block_grads* G, const
     return CREAM_OK;
 }
 
-int cream_block_wgrad_bf16(int on)
-{
-    const int prev = wgrad_bf16_mode();
-    if (on >= 0) g_wgrad_bf16.store(on != 0, std::memory_order_relaxed);
-    return prev;
-}
-
+int cream_block_wgrad_bf16(int on) { return g_wgrad_bf16.set(on); }
 
 int cream_block_prof_enable(int on)
 {

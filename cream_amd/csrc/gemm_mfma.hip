@@ -25,6 +25,7 @@
 #include "gemm_tn8.hpp"
 #include "launch_ev.hpp"
 #include "cu_budget.hpp"
+#include "env_switch.hpp"
 
 namespace {
 std::atomic<int> g_cu_reserve{0};
@@ -62,50 +63,23 @@ int num_cus() { return cream::cu_count(); }
 // 256 x 256 macro tile (8 waves, 128 x 64 wave tiles, 128 KB of LDS, one persistent workgroup per CU) for the wide
 // outputs (qkv, fc1, fc2 dgrad: N >= 960): half the L2 -> LDS bytes per flop of the 128 x 128 tile.
 // CREAM_GEMM_NT256 in the environment / cream_gemm_nt256() switch it (A/B runs); default: see nt256_mode().
-std::atomic<int> g_nt256{-1};
-int nt256_mode()
-{
-    int m = g_nt256.load(std::memory_order_relaxed);
-    if (m < 0) {
-        const char* e = getenv("CREAM_GEMM_NT256");
-        // default 2: with COLD operands (rotating buffer sets, profiles/r04_gemm_probe_cold.txt) the macro tile is 6-14 % faster
-        // than the 128-wide tiles where the contraction is long (fc2, fc1 dgrad, qkv dgrad: K = 1152 .. 1792, N = E) and
-        // equal or slower on the wide-output shapes (mode 1) — the warm-buffer probe of the same kernels had it the other way
-        // round.  Same-box A/B of the step, alternating, twice: 9.455 / 9.502 -> 9.351 / 9.402 ms (-1.0 %).
-        m = e ? atoi(e) : 2;
-        g_nt256.store(m, std::memory_order_relaxed);
-    }
-    return m;
-}
+// default 2: with COLD operands (rotating buffer sets, profiles/r04_gemm_probe_cold.txt) the macro tile is 6-14 % faster
+// than the 128-wide tiles where the contraction is long (fc2, fc1 dgrad, qkv dgrad: K = 1152 .. 1792, N = E) and
+// equal or slower on the wide-output shapes (mode 1) — the warm-buffer probe of the same kernels had it the other way
+// round.  Same-box A/B of the step, alternating, twice: 9.455 / 9.502 -> 9.351 / 9.402 ms (-1.0 %).
+EnvSwitch g_nt256{"CREAM_GEMM_NT256", 2};
+int nt256_mode() { return g_nt256.get(); }
 
 // Round 6: the two-stage kernels with their tile epilogue off the memory counters (gemm_mfma.hpp, "OPT"): asm LDS-DMA, LDS-only
 // epilogue barriers, side inputs requested under the first K-step, counted wait for the first K-step behind an epilogue
 // (bit 0), and gelu / gelu' of the fc1 epilogue from a 16 KB LDS table instead of ~31 VALU instructions per element (bit 1).
 // Outputs are bit-identical to the OPT = 0 kernels (test_nt_epilogue_variants_are_bit_identical, exhaustive over the bf16
 // values for the table).  CREAM_GEMM_NTOPT in the environment / cream_gemm_ntopt(): 0 = off, 1 = bit 0, 3 = both (default).
-std::atomic<int> g_ntopt{-1};
-int ntopt_mode()
-{
-    int m = g_ntopt.load(std::memory_order_relaxed);
-    if (m < 0) {
-        const char* e = getenv("CREAM_GEMM_NTOPT");
-        m = e ? atoi(e) : 3;
-        g_ntopt.store(m, std::memory_order_relaxed);
-    }
-    return m;
-}
+EnvSwitch g_ntopt{"CREAM_GEMM_NTOPT", 3, [](int m) { return m & 15; }};
+int ntopt_mode() { return g_ntopt.get(); }
 // CREAM_GEMM_STAGGER / cream_gemm_stagger(): the second half of a two-workgroups-per-CU grid starts n x 64 clocks late
-std::atomic<int> g_stagger{-1};
-int stagger_mode()
-{
-    int m = g_stagger.load(std::memory_order_relaxed);
-    if (m < 0) {
-        const char* e = getenv("CREAM_GEMM_STAGGER");
-        m = e ? atoi(e) : 0;
-        g_stagger.store(m, std::memory_order_relaxed);
-    }
-    return m;
-}
+EnvSwitch g_stagger{"CREAM_GEMM_STAGGER", 0};
+int stagger_mode() { return g_stagger.get(); }
 
 template <int EPI>
 int launch_nt256(const NtParams& p, hipStream_t st)
@@ -122,17 +96,8 @@ int launch_nt256(const NtParams& p, hipStream_t st)
 
 // the counted-vmcnt, phase-interleaved kernel (gemm_nt8.hpp): 256 x 256 tiles, one persistent 8-wave workgroup per CU.
 // CREAM_GEMM_NT8 in the environment / cream_gemm_nt8(): 0 = never, 1 = wherever its limits allow, 2 = by shape (nt8_wanted)
-std::atomic<int> g_nt8{-1};
-int nt8_mode()
-{
-    int m = g_nt8.load(std::memory_order_relaxed);
-    if (m < 0) {
-        const char* e = getenv("CREAM_GEMM_NT8");
-        m = e ? atoi(e) : 4;
-        g_nt8.store(m, std::memory_order_relaxed);
-    }
-    return m;
-}
+EnvSwitch g_nt8{"CREAM_GEMM_NT8", 4};
+int nt8_mode() { return g_nt8.get(); }
 
 bool nt8_fits(const NtParams& p)
 {
@@ -164,18 +129,9 @@ int launch_nt8(const NtParams& p, hipStream_t st)
 // 98 more registers than a wave has.  E = 448 stays on the 256-wide tiles (12 % padding).
 // Same contraction order per output element as every other tile: bit-identical results.
 // CREAM_GEMM_NTHALF in the environment / cream_gemm_nthalf(): 0 = off, 1 = on (plain and bias epilogues, M >= 1024).
-std::atomic<int> g_nthalf{-1};
-int nthalf_mode()
-{
-    int m = g_nthalf.load(std::memory_order_relaxed);
-    if (m < 0) {
-        const char* e = getenv("CREAM_GEMM_NTHALF");
-        // default 1: same-call step A/B x3 (profiles/r06_nt_256x192.md): 8.945 / 8.952 / 8.903 -> 8.763 / 8.770 / 8.770 ms (-2.0 %)
-        m = e ? atoi(e) : 1;
-        g_nthalf.store(m, std::memory_order_relaxed);
-    }
-    return m;
-}
+// default 1: same-call step A/B x3 (profiles/r06_nt_256x192.md): 8.945 / 8.952 / 8.903 -> 8.763 / 8.770 / 8.770 ms (-2.0 %)
+EnvSwitch g_nthalf{"CREAM_GEMM_NTHALF", 1, norm_bool};
+int nthalf_mode() { return g_nthalf.get(); }
 
 template <int EPI, int BN, int WM, int WN>
 int launch_nt_half(const NtParams& p, hipStream_t st)
@@ -285,40 +241,11 @@ extern "C" {
 
 int cream_gemm_rows_per_colsum_slab(void) { return 128; }
 
-int cream_gemm_nt256(int on)
-{
-    const int prev = nt256_mode();
-    if (on >= 0) g_nt256.store(on, std::memory_order_relaxed);
-    return prev;
-}
-
-int cream_gemm_nthalf(int on)
-{
-    const int prev = nthalf_mode();
-    if (on >= 0) g_nthalf.store(on != 0, std::memory_order_relaxed);
-    return prev;
-}
-
-int cream_gemm_ntopt(int mode)
-{
-    const int prev = ntopt_mode();
-    if (mode >= 0) g_ntopt.store(mode & 15, std::memory_order_relaxed);
-    return prev;
-}
-
-int cream_gemm_stagger(int n)
-{
-    const int prev = stagger_mode();
-    if (n >= 0) g_stagger.store(n, std::memory_order_relaxed);
-    return prev;
-}
-
-int cream_gemm_nt8(int mode)
-{
-    const int prev = nt8_mode();
-    if (mode >= 0) g_nt8.store(mode, std::memory_order_relaxed);
-    return prev;
-}
+int cream_gemm_nt256(int on) { return g_nt256.set(on); }
+int cream_gemm_nthalf(int on) { return g_nthalf.set(on); }
+int cream_gemm_ntopt(int mode) { return g_ntopt.set(mode); }
+int cream_gemm_stagger(int n) { return g_stagger.set(n); }
+int cream_gemm_nt8(int mode) { return g_nt8.set(mode); }
 
 int cream_linear_fwd(void* out, const void* x, const void* w, const void* bias, int M, int N, int K, int64_t ldw,
                      void* stream)
@@ -399,17 +326,8 @@ int cream_linear_dgrad_mul(void* dh, float* colsum_parts, const void* dy, const 
 namespace {
 // the weight-gradient product on the macro tile of gemm_tn8.hpp (bf16 partial tiles, no bias partials).
 // CREAM_GEMM_TN8 in the environment / cream_gemm_tn8(): 0 = never, 1 = problems of at least six 256 x 256 tiles, 2 = every problem (default)
-std::atomic<int> g_tn8{-1};
-int tn8_mode()
-{
-    int m = g_tn8.load(std::memory_order_relaxed);
-    if (m < 0) {
-        const char* e = getenv("CREAM_GEMM_TN8");
-        m = e ? atoi(e) : 2;
-        g_tn8.store(m, std::memory_order_relaxed);
-    }
-    return m;
-}
+EnvSwitch g_tn8{"CREAM_GEMM_TN8", 2};
+int tn8_mode() { return g_tn8.get(); }
 int tn8_tiles(int N, int K) { return ((N + 255) / 256) * ((K + 255) / 256); }
 // one workgroup per CU: as many token slices as fit the chip once
 int tn8_splits(int M, int N, int K)
@@ -440,11 +358,8 @@ extern "C" {
 
 int cream_gemm_tn8(int mode)
 {
-    const int prev = tn8_mode();
-    if (mode >= 0 && mode != prev) {
-        g_tn8.store(mode, std::memory_order_relaxed);
-        g_layout_epoch.fetch_add(1, std::memory_order_relaxed);
-    }
+    const int prev = g_tn8.set(mode);
+    if (mode >= 0 && mode != prev) g_layout_epoch.fetch_add(1, std::memory_order_relaxed);
     return prev;
 }
 

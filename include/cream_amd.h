@@ -89,7 +89,7 @@ int cream_attn_rpe2d_padded_len(int N);
 int cream_attn_rpe2d_dtab_parts(int B, int H);
 
 /* Which backward runs for the AutoFormer geometry (N = 197, 14 x 14 grid, max_relative_position 14) in bf16:
- * 0 = the two-launch backward; 1 = the one-pass kernel (csrc/attn_rpe2d_bwd1.hpp: K, V, Q, dO of one (b, h) whole in LDS, P / dS
+ * 0 = the two-launch backward (csrc/attn_rpe2d_bwd.hpp); 1 = the one-pass kernel (csrc/attn_rpe2d_bwd1.hpp: K, V, Q, dO of one (b, h) whole in LDS, P / dS
  * exchanged between the query-tile and key-tile owners through LDS; the side buffers dlt / qe / de / delta are not used as
  * such — the first 32 KB of dlt carry the bf16 operand images of the tables); 2 = the same pass with the two roles on separate
  * waves (csrc/attn_rpe2d_bwd2.hpp: 7 query-tile owners + 5 waves sharing the 14 key-side jobs, the table gradients accumulated in
@@ -160,7 +160,7 @@ int cream_attn_rpe2d_bwd(void* dq, void* dk, void* dv, int64_t dsb, int64_t dsn,
  *   - forward, AutoFormer geometry (N = 197, 14 x 14 grid, mr = 14) in bf16: runs csrc/attn_rpe2d_fwd2.hpp — 32-key tiles with
  *     an online (lazy-maximum) softmax, two 7-wave half-workgroups per CU in ping-pong (one multiplies while the other does
  *     the element-wise / memory work), K / V by LDS-DMA; without an image (or with cream_attn_rpe2d_fwd_mode(0)) the
- *     whole-row-block kernel attn_rpe2d_fwd14 runs.  Same outputs up to the rounding of the softmax numerators' reference
+ *     whole-row-block kernel attn_rpe2d_fwd14 (csrc/attn_rpe2d_fwd14.hpp) runs.  Same outputs up to the rounding of the softmax numerators' reference
  *     point (both within the bf16 bounds of tests/test_attn_gpu.py).
  *   - backward (one-pass kernel): reads the image instead of building one into dlt with an extra launch.
  * cream_attn_rpe2d_fwd_mode(1 | 0): as above; < 0 queries; returns the previous value; initial: CREAM_ATTN_FWD2, else 1. */

@@ -141,13 +141,48 @@ def test_new_entry_points_validate_arguments_without_launching():
     assert 1 <= lib.cream_attn_rpe2d_dtab_parts(128, 6) <= 768
 
 
+# the process-wide kernel-choice switches: entry point -> (environment variable of the initial value, a documented non-default value)
+_SWITCHES = {"cream_gemm_nt256": ("CREAM_GEMM_NT256", 1), "cream_gemm_nthalf": ("CREAM_GEMM_NTHALF", 0),
+             "cream_gemm_ntopt": ("CREAM_GEMM_NTOPT", 1), "cream_gemm_stagger": ("CREAM_GEMM_STAGGER", 2),
+             "cream_gemm_nt8": ("CREAM_GEMM_NT8", 2), "cream_gemm_tn8": ("CREAM_GEMM_TN8", 1),
+             "cream_attn_rpe2d_fwd_mode": ("CREAM_ATTN_FWD2", 0), "cream_attn_rpe2d_bwd_mode": ("CREAM_ATTN_BWD1", 1),
+             "cream_block_wgrad_bf16": ("CREAM_WGRAD_BF16", 0)}
+
+
+def test_switches_take_their_initial_value_from_the_environment():
+    """A fresh process with every switch's variable set reports those values (read once, on first use)."""
+    import json
+    import subprocess
+    import sys
+    from cream_amd import _lib
+    _lib.load()
+    env = dict(os.environ, **{var: str(val) for var, val in _SWITCHES.values()})
+    code = ("import ctypes, json, sys\nlib = ctypes.CDLL(sys.argv[1])\n"
+            "print(json.dumps({n: getattr(lib, n)(-1) for n in sys.argv[2:]}))")
+    out = subprocess.run([sys.executable, "-c", code, _lib.LIB_PATH] + list(_SWITCHES), env=env, capture_output=True, text=True,
+                         check=True, timeout=120).stdout
+    assert json.loads(out) == {name: val for name, (_, val) in _SWITCHES.items()}
+
+
 def test_switches_without_a_device():
     """Entry points that take no device pointers: the process-wide kernel-choice switches (each returns the previous value)."""
     from cream_amd import _lib
     lib = _lib.load()
-    for fn in (lib.cream_gemm_nt8, lib.cream_gemm_tn8, lib.cream_gemm_nt256, lib.cream_block_wgrad_bf16):
-        prev = fn(-1)
-        assert fn(1) == prev and fn(prev) == 1 and fn(-1) == prev
+    fns = {name: getattr(lib, name) for name in _SWITCHES}
+    start = {name: fn(-1) for name, fn in fns.items()}
+    try:
+        for name, fn in fns.items():
+            prev = start[name]
+            assert fn(1) == prev and fn(prev) == 1 and fn(-1) == prev, name
+        # values outside a switch's range are mapped onto it when they are set
+        for name, given, stored in (("cream_gemm_nthalf", 5, 1), ("cream_gemm_ntopt", 19, 3), ("cream_attn_rpe2d_bwd_mode", 3, 1),
+                                    ("cream_attn_rpe2d_fwd_mode", 7, 1), ("cream_block_wgrad_bf16", 2, 1)):
+            assert fns[name](given) == start[name] and fns[name](-1) == stored, name
+            assert fns[name](start[name]) == stored
+    finally:
+        for name, fn in fns.items():
+            fn(start[name])
+    assert {name: fn(-1) for name, fn in fns.items()} == start
     # one token slice per workgroup: the macro-tile kernel of the weight gradients takes fewer, longer slices than the 128 x 128 one
     assert 1 <= lib.cream_linear_wgrad_splits_bf16(25216, 1344, 384) <= lib.cream_linear_wgrad_splits(25216, 1344, 384)
     assert lib.cream_linear_wgrad_splits_bf16(0, 8, 8) == 0
