@@ -119,6 +119,9 @@ SIGNATURES = {
     "cream_linear_wgrad_splits_bf16": (_i, [_i, _i, _i]),
     "cream_gemm_tn8": (_i, [_i]),
     "cream_gemm_nthalf": (_i, [_i]),
+    "cream_gemm_nt224": (_i, [_i]),
+    "cream_gemm_nt224_launches": (_i64, []),
+    "cream_linear_nt224": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i64, _i, _i64, _i, _i64, _vp]),
     "cream_gemm_ntopt": (_i, [_i]),
     "cream_gemm_stagger": (_i, [_i]),
     "cream_block_layout_epoch": (_i, []),

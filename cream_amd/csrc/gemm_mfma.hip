@@ -22,6 +22,7 @@
 #include "cream_amd.h"
 #include "gemm_mfma.hpp"
 #include "gemm_nt8.hpp"
+#include "gemm_nt224.hpp"
 #include "gemm_tn8.hpp"
 #include "launch_ev.hpp"
 #include "cu_budget.hpp"
@@ -145,10 +146,51 @@ int launch_nt_half(const NtParams& p, hipStream_t st)
     return hipGetLastError() == hipSuccess ? CREAM_OK : CREAM_ERR_LAUNCH;
 }
 
+// A 256 x 224 tile on 16x16x32 MFMAs (gemm_nt224.hpp: 4 x 2 waves of 64 x 112, 120 KB of LDS, one persistent workgroup per CU)
+// for the products whose output is 448 wide (proj, fc2, the fc1 / qkv input gradients at E = 448; the proj input gradient at 7 heads
+// at every E): two column tiles without padding where the 256-wide tiles carry 12.5 % and the 128 x 64 tile has the worst operand
+// ingest per flop.  233 VGPRs, no scratch.
+// Routing rule (launch_nt, ahead of the nt8 / nt256 / 128-wide choices): plain and bias epilogues, M >= 1024, and
+//   * N == 448 for every K;
+//   * N == 1344 with the bias epilogue in row segments of 448 (qkv forward at 7 heads: two whole column tiles per segment).
+// Cold probe at M = 25,216 (profiles/NOTES_nt_256x224.md; kernel chosen before -> this tile, us):
+//   bias epilogue (was gemm_nt8)          K 320 17.3 -> 15.5   384 19.2 -> 17.3   448 20.6 -> 18.6   960 34.4 -> 31.0   1152 38.5 -> 35.3
+//                                         1344 43.0 -> 39.6   1568 52.0 -> 50.8 (tail K-step pinned; 48.9 -> 50.0 before)   1792 51.9 -> 50.4
+//   plain store (was 128 x 64 / 256 x 256) K 320 20.5 -> 15.5   384 23.5 -> 17.1   448 25.9 -> 18.8   960 45.2 -> 30.8   1152 39.2 -> 34.8
+//                                         1344 43.6 -> 39.1   1568 50.7 -> 49.3   1792 55.4 -> 50.6
+//   qkv forward N 1344 K 448 (was gemm_nt8) 50.6 -> 45.1
+// Same-call step A/B x4, alternating, switch off -> on: 8.457 / 8.443 / 8.484 / 8.440 -> 8.317 / 8.369 / 8.317 / 8.341 ms (-1.4 %; an
+// earlier build with the K = 1568 bias product still on gemm_nt8, another GPU: 8.265 / 8.246 / 8.255 / 8.258 -> 8.231 / 8.210 / 8.214 / 8.219).
+// Counters: HBM read per launch equals that of the kernel chosen before on the same shape (FETCH_SIZE 13,034 against 13,062 KiB at
+// K = 448, 38,898 against 38,901 at K = 1344); the main loop adds no LDS bank-conflict cycle.
+// Numerics: the 16x16x32 instruction adds 32 contraction elements per issue, every other tile adds 16 — the one tile that does not
+// keep the "same contraction order as every other tile" property: on general operands a routed product may differ from the other
+// tiles' result in the last bf16 place (exact operands: bit-identical, tests/test_gemm_nt224_gpu.py; on the random operands of that
+// test and of the probe no element differed).
+// CREAM_GEMM_NT224 in the environment / cream_gemm_nt224(): 0 = off, 1 = on (default).  No workspace layout depends on it.
+EnvSwitch g_nt224{"CREAM_GEMM_NT224", 1, norm_bool};
+int nt224_mode() { return g_nt224.get(); }
+std::atomic<int64_t> g_nt224_launches{0};   // cream_gemm_nt224_launches(): lets a test see which kernel a routed call reached
+
+template <int EPI>
+int launch_nt224(const NtParams& p, hipStream_t st)
+{
+    auto kern = gemm_nt224_kernel<EPI>;
+    if (!cream::raise_dynamic_lds(kern, NT224_LDS_BYTES)) return CREAM_ERR_LAUNCH;
+    const int tiles = ((p.M + NT224_BM - 1) / NT224_BM) * ((p.N + NT224_BN - 1) / NT224_BN), slots = num_cus() / 8 * 8;
+    CREAM_LAUNCH(kern, dim3(tiles < slots ? tiles : slots), dim3(512), NT224_LDS_BYTES, st, p);
+    g_nt224_launches.fetch_add(1, std::memory_order_relaxed);
+    return hipGetLastError() == hipSuccess ? CREAM_OK : CREAM_ERR_LAUNCH;
+}
+
 template <int EPI>
 int launch_nt(const NtParams& p, hipStream_t st)
 {
     if constexpr (EPI == EPI_STORE || EPI == EPI_BIAS) {
+        if (nt224_mode() > 0 && p.M >= 1024) {
+            if (p.N == 448) return launch_nt224<EPI>(p, st);
+            if (EPI == EPI_BIAS && p.N == 1344 && p.nseg == 448) return launch_nt224<EPI>(p, st);
+        }
         if (nthalf_mode() > 0 && p.M >= 1024) {
             if (p.N == 384 || p.N == 320) return launch_nt_half<EPI, 192, 4, 2>(p, st);
         }
@@ -243,6 +285,8 @@ int cream_gemm_rows_per_colsum_slab(void) { return 128; }
 
 int cream_gemm_nt256(int on) { return g_nt256.set(on); }
 int cream_gemm_nthalf(int on) { return g_nthalf.set(on); }
+int cream_gemm_nt224(int on) { return g_nt224.set(on); }
+int64_t cream_gemm_nt224_launches(void) { return g_nt224_launches.load(std::memory_order_relaxed); }
 int cream_gemm_ntopt(int mode) { return g_ntopt.set(mode); }
 int cream_gemm_stagger(int n) { return g_stagger.set(n); }
 int cream_gemm_nt8(int mode) { return g_nt8.set(mode); }
@@ -267,6 +311,24 @@ int cream_linear_fwd_seg(void* out, const void* x, const void* w, const void* bi
     p.bias = (const uint16_t*)bias;
     p.nseg = nseg; p.nseg_stride = nseg_stride;
     return launch_nt<EPI_BIAS>(p, (hipStream_t)stream);
+}
+
+int cream_linear_nt224(void* out, const void* x, const void* w, const void* bias, int M, int N, int K, int64_t ldw, int nseg,
+                       int64_t nseg_stride, int kseg, int64_t kseg_stride, void* stream)
+{
+    const int rc = check_nt(out, x, w, M, N, K, ldw, kseg > 0 && kseg < K ? kseg : K);
+    if (rc) return rc < 0 ? rc : CREAM_OK;
+    NtParams p = plain(out, x, w, M, N, K, ldw);
+    if (nseg > 0) {
+        if (nseg % 8 || (int64_t)3 * nseg < N || nseg_stride % 8) return CREAM_ERR_BAD_ARG;
+        p.nseg = nseg; p.nseg_stride = nseg_stride;
+    }
+    if (kseg > 0) {
+        if (kseg % 64 || K % kseg || kseg_stride % 8) return CREAM_ERR_BAD_ARG;
+        p.kseg = kseg; p.kseg_stride = kseg_stride;
+    }
+    p.bias = (const uint16_t*)bias;
+    return bias ? launch_nt224<EPI_BIAS>(p, (hipStream_t)stream) : launch_nt224<EPI_STORE>(p, (hipStream_t)stream);
 }
 
 int cream_linear_gelu_fwd_pad(void* gp, void* g, const void* x, const void* w, const void* bias, int M, int N, int Nvalid,

@@ -632,6 +632,22 @@ int cream_gemm_nt256(int on);
 /* Round 6: 256 x (E / 2) tiles (column tiles that divide N) for the plain / bias products whose output is 320 / 384 / 448 wide
  * (csrc/gemm_mfma.hip: launch_nt_half).  1 = on, 0 = off, < 0 queries; returns the previous value; initial: CREAM_GEMM_NTHALF. */
 int cream_gemm_nthalf(int on);
+/* A 256 x 224 tile on v_mfma_f32_16x16x32_bf16 (csrc/gemm_nt224.hpp, launch_nt224 in csrc/gemm_mfma.hip) for the plain / bias
+ * products whose output is 448 wide at M >= 1024 (proj, fc2 and the fc1 / qkv / proj input gradients at embed dim 448; the proj
+ * input gradient at 7 heads) and for cream_linear_fwd_seg with N = 1344 in
+ * segments of 448 (qkv forward at 7 heads).  1 = on (default), 0 = off, < 0 queries; returns the previous value; initial:
+ * CREAM_GEMM_NT224.
+ * This instruction adds 32 contraction elements per issue, the other tiles 16: on general operands a routed product may differ
+ * from the switch-off result in the last bf16 place.  No workspace layout depends on the switch. */
+int cream_gemm_nt224(int on);
+/* Launches of that tile by this process so far (routed calls and cream_linear_nt224): a test reads it around a call to see
+ * which kernel the call reached. */
+int64_t cream_gemm_nt224_launches(void);
+/* The same tile on any problem, whatever the switches say (tests, probes): out(M x N) = x(M x K) . W(N x K)^T + bias (bias may be
+ * NULL: plain store).  nseg > 0: rows of W in segments as cream_linear_fwd_seg; kseg > 0: the contraction in segments as
+ * cream_linear_dgrad_seg (K % kseg == 0, kseg % 64 == 0); 0 = one segment.  M arbitrary, N % 8 == K % 8 == ldw % 8 == 0. */
+int cream_linear_nt224(void* out, const void* x, const void* w, const void* bias, int M, int N, int K, int64_t ldw, int nseg,
+                       int64_t nseg_stride, int kseg, int64_t kseg_stride, void* stream);
 int cream_gemm_nt8(int mode);
 /* Round 6: the two-stage NT kernels with their tile epilogue taken off the memory counters (csrc/gemm_mfma.hpp, "OPT"):
  * bit 0 = LDS-DMA as asm, LDS-only epilogue barriers, side inputs (bias, the x gelu' factor rows) requested under the first
