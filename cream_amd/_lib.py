@@ -61,6 +61,11 @@ SIGNATURES = {
     "cream_window_attn_blocks": (_i, [_vp]),
     "cream_window_attn_fwd": (_i, [_vp, _vp]),
     "cream_window_attn_bwd": (_i, [_vp, _vp]),
+    "cream_window_attn_large_check": (_i, [_vp, _i]),
+    "cream_window_attn_large_part_size": (_i, [_i, _i]),
+    "cream_window_attn_large_blocks": (_i, [_vp]),
+    "cream_window_attn_large_fwd": (_i, [_vp, _vp]),
+    "cream_window_attn_large_bwd": (_i, [_vp, _vp]),
     "cream_relation_loss_check": (_i, [_vp]),
     "cream_relation_loss_blocks": (_i, [_vp]),
     "cream_relation_loss": (_i, [_vp, _vp]),
@@ -232,6 +237,16 @@ class WindowAttnDesc(ctypes.Structure):
     """struct cream_window_attn_desc of include/cream_amd.h."""
     _fields_ = ([(n, _vp) for n in ("q", "k", "v")] + [(n, _i64) for n in ("sb", "sn", "sh")] +
                 [(n, _vp) for n in ("out", "lse", "table", "wl", "bl", "ww", "bw")] +
+                [(n, _c.c_int32) for n in ("B", "H", "Hs", "Ws", "w", "shift", "mask_shift", "head_dim")] +
+                [("scale", _f), ("part_blocks", _c.c_int32)] +
+                [(n, _vp) for n in ("dout", "dq", "dk", "dv")] + [(n, _i64) for n in ("dsb", "dsn", "dsh")] +
+                [(n, _vp) for n in ("delta", "part")])
+
+
+class WindowAttnLargeDesc(ctypes.Structure):
+    """struct cream_window_attn_large_desc of include/cream_amd.h."""
+    _fields_ = ([(n, _vp) for n in ("q", "k", "v")] + [(n, _i64) for n in ("sb", "sn", "sh")] +
+                [(n, _vp) for n in ("out", "lse", "table")] +
                 [(n, _c.c_int32) for n in ("B", "H", "Hs", "Ws", "w", "shift", "mask_shift", "head_dim")] +
                 [("scale", _f), ("part_blocks", _c.c_int32)] +
                 [(n, _vp) for n in ("dout", "dq", "dk", "dv")] + [(n, _i64) for n in ("dsb", "dsn", "dsh")] +

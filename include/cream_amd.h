@@ -401,6 +401,49 @@ int cream_window_attn_fwd(const cream_window_attn_desc* d, void* stream);
 /* dq, dk, dv and the partials of the parameter gradients from dout and lse.  Two launches. */
 int cream_window_attn_bwd(const cream_window_attn_desc* d, void* stream);
 
+/* ---- fused (shifted-)window attention for windows of 9x9 .. 14x14 (csrc/window_attn_large.hip) ---------------------
+ * WindowAttention.forward of AutoFormerV2 / S3 between the qkv and proj linears (AutoFormerV2/model/SSS.py:106-137), with
+ * the geometry of cream_window_attn_desc in the addressing:
+ *     S_h = (s q_h) k_h^T + table[rel(i,j), h] (+ mask in {0, -100}),  P_h = softmax(S_h),  O_h = P_h v_h.
+ * bf16 operands, fp32 accumulation; head_dim 32, 1 <= H <= 32 independent heads (no head transforms), square windows with
+ * 9 <= w <= 14, Hs and Ws multiples of w, shift < w, mask_shift < w.  Anything else returns CREAM_ERR_BAD_ARG before any
+ * HIP call; B == 0 is a no-op.  NP = w * w rounded up to a multiple of 32.  Nothing of size N^2 per window is written; no
+ * global atomics: d table comes as (part_blocks, (2w-1)^2, H) fp32 partials, every entry written once, which the caller
+ * sums over the first axis. */
+typedef struct cream_window_attn_large_desc {
+    const void *q, *k, *v;          /* bf16; element (b, n, h, :) at ptr[b*sb + n*sn + h*sh]                 */
+    int64_t sb, sn, sh;
+    void* out;                      /* (B, Hs*Ws, H, 32) bf16 (fwd only)                                   */
+    float* lse;                     /* (B * nW, H, NP): log-sum-exp of the masked logits (fwd: out, bwd: in) */
+    const float* table;             /* ((2w-1)^2, H) fp32                                                  */
+    int32_t B, H, Hs, Ws, w, shift, mask_shift, head_dim;
+    float scale;
+    int32_t part_blocks;            /* bwd: cream_window_attn_large_blocks(d), the first axis of `part`     */
+    /* backward only */
+    const void* dout;               /* (B, Hs*Ws, H, 32) bf16                                              */
+    void *dq, *dk, *dv;             /* bf16; element (b, n, h, :) at ptr[b*dsb + n*dsn + h*dsh]             */
+    int64_t dsb, dsn, dsh;
+    float* delta;                   /* (B * nW, H, NP) fp32 out: sum_j P dP of every query                 */
+    float* part;                    /* (part_blocks, cream_window_attn_large_part_size(H, w)) fp32 out      */
+} cream_window_attn_large_desc;
+
+/* The argument check of the calls below alone (backward != 0: of cream_window_attn_large_bwd, except part_blocks'
+ * value): CREAM_OK or the error code.  Pure host arithmetic. */
+int cream_window_attn_large_check(const cream_window_attn_large_desc* d, int backward);
+
+/* Floats per partial, (2w-1)^2 H, or CREAM_ERR_BAD_ARG.  Pure host arithmetic. */
+int cream_window_attn_large_part_size(int H, int w);
+
+/* Partials of d table for this descriptor's shape (B, H, Hs, Ws, w): the persistent grids have this many workgroups per
+ * head (from cream_cu_count(); the data pointers are not looked at), 0 when B == 0, or an error code. */
+int cream_window_attn_large_blocks(const cream_window_attn_large_desc* d);
+
+/* out and lse from q, k, v.  One launch. */
+int cream_window_attn_large_fwd(const cream_window_attn_large_desc* d, void* stream);
+
+/* dq, dk, dv, delta and the partials of d table from dout and lse.  Two launches. */
+int cream_window_attn_large_bwd(const cream_window_attn_large_desc* d, void* stream);
+
 /* ---- the relation losses of the Mini-Swin distillation step (csrc/distill_loss.hip) -------------------------------
  * cal_relation_loss and cal_hidden_relation_loss of MiniViT/Mini-Swin/main.py:39-57 and :66-77, each with the gradient
  * with respect to the student in the same call.  No atomics: one fp32 partial of the (already scaled) loss per workgroup,
