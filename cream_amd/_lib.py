@@ -66,6 +66,10 @@ SIGNATURES = {
     "cream_window_attn_large_blocks": (_i, [_vp]),
     "cream_window_attn_large_fwd": (_i, [_vp, _vp]),
     "cream_window_attn_large_bwd": (_i, [_vp, _vp]),
+    "cream_token_dwconv3_part_size": (_i, [_i]),
+    "cream_token_dwconv3_blocks": (_i, [_vp]),
+    "cream_token_dwconv3_fwd": (_i, [_vp, _vp]),
+    "cream_token_dwconv3_bwd": (_i, [_vp, _vp]),
     "cream_relation_loss_check": (_i, [_vp]),
     "cream_relation_loss_blocks": (_i, [_vp]),
     "cream_relation_loss": (_i, [_vp, _vp]),
@@ -251,6 +255,13 @@ class WindowAttnLargeDesc(ctypes.Structure):
                 [("scale", _f), ("part_blocks", _c.c_int32)] +
                 [(n, _vp) for n in ("dout", "dq", "dk", "dv")] + [(n, _i64) for n in ("dsb", "dsn", "dsh")] +
                 [(n, _vp) for n in ("delta", "part")])
+
+
+class TokenDwconv3Desc(ctypes.Structure):
+    """struct cream_token_dwconv3_desc of include/cream_amd.h."""
+    _fields_ = ([(n, _vp) for n in ("x", "w", "bias", "y")] +
+                [(n, _c.c_int32) for n in ("B", "Hs", "Ws", "C", "dtype", "part_blocks")] +
+                [(n, _vp) for n in ("dy", "dx", "part")])
 
 
 class RelationSide(ctypes.Structure):

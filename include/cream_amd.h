@@ -444,6 +444,43 @@ int cream_window_attn_large_fwd(const cream_window_attn_large_desc* d, void* str
 /* dq, dk, dv, delta and the partials of d table from dout and lse.  Two launches. */
 int cream_window_attn_large_bwd(const cream_window_attn_large_desc* d, void* stream);
 
+/* ---- depthwise 3 x 3 convolution on the token layout (csrc/token_dwconv.hip) -----------------------------------------
+ * The local convolution of a TinyViT block (TinyViT/models/tiny_vit.py:333-335, :374-376) without the transposes to NCHW and
+ * back: x (B, Hs*Ws, C) contiguous, token n = i * Ws + j; stride 1, zero padding 1:
+ *     y[b, i, j, c]  = bias[c] + sum_{di, dj} w[c, di, dj] x[b, i + di - 1, j + dj - 1, c]
+ *     dx[b, i, j, c] = sum_{di, dj} w[c, di, dj] dy[b, i - di + 1, j - dj + 1, c]
+ *     dw[c, di, dj]  = sum_{b, i, j} dy[b, i, j, c] x[b, i + di - 1, j + dj - 1, c],   dbias[c] = sum_{b, i, j} dy[b, i, j, c]
+ * x, y, dy, dx in `dtype` (CREAM_BF16 or CREAM_F32), taps, bias and the partials fp32; fp32 accumulation, bias first, then
+ * the taps in row-major order.  C a multiple of 8, B, Hs, Ws >= 1, every base 16-byte aligned (bias: 4); anything else
+ * returns CREAM_ERR_BAD_ARG (CREAM_ERR_BAD_DTYPE) before any HIP call.  No atomics: dw and dbias come as (part_blocks,
+ * cream_token_dwconv3_part_size(C)) fp32 partials [dw (C, 9) | dbias (C)], every entry written once, which the caller sums
+ * over the first axis. */
+typedef struct cream_token_dwconv3_desc {
+    const void* x;                  /* (B, Hs*Ws, C)                                                        */
+    const float* w;                 /* (C, 1, 3, 3) fp32 contiguous                                         */
+    const float* bias;              /* (C) fp32 or NULL (fwd only)                                          */
+    void* y;                        /* (B, Hs*Ws, C) (fwd only)                                             */
+    int32_t B, Hs, Ws, C, dtype;
+    int32_t part_blocks;            /* bwd: cream_token_dwconv3_blocks(d), the first axis of `part`         */
+    /* backward only */
+    const void* dy;                 /* (B, Hs*Ws, C)                                                        */
+    void* dx;                       /* (B, Hs*Ws, C)                                                        */
+    float* part;                    /* (part_blocks, 10 C) fp32 out                                         */
+} cream_token_dwconv3_desc;
+
+/* Floats per partial, 10 C, or CREAM_ERR_BAD_ARG.  Pure host arithmetic. */
+int cream_token_dwconv3_part_size(int C);
+
+/* Workgroups along the token axis of the gradient launch for this descriptor's shape (B, Hs, Ws, C, dtype; from
+ * cream_cu_count(); the data pointers are not looked at), or an error code. */
+int cream_token_dwconv3_blocks(const cream_token_dwconv3_desc* d);
+
+/* y from x, w and bias.  One launch. */
+int cream_token_dwconv3_fwd(const cream_token_dwconv3_desc* d, void* stream);
+
+/* dx and the partials of dw and dbias from dy and x.  Two launches. */
+int cream_token_dwconv3_bwd(const cream_token_dwconv3_desc* d, void* stream);
+
 /* ---- the relation losses of the Mini-Swin distillation step (csrc/distill_loss.hip) -------------------------------
  * cal_relation_loss and cal_hidden_relation_loss of MiniViT/Mini-Swin/main.py:39-57 and :66-77, each with the gradient
  * with respect to the student in the same call.  No atomics: one fp32 partial of the (already scaled) loss per workgroup,
