@@ -147,6 +147,8 @@ SIGNATURES = {
     "cream_adamw_step_clipped": (_i, [_vp, _vp, _i, _i, _i, _c.c_double, _c.c_double, _c.c_double, _c.c_double, _i64, _vp, _vp]),
     "cream_grad_scale": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "cream_soft_ce": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp]),
+    "cream_sparse_ce": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp]),
+    "cream_softmax_topk_records": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "cream_linear_f32_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i64, _i64, _i, _i, _vp]),
     "cream_bmm_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp]),
     "cream_linear_f32_dgrad": (_i, [_vp, _vp, _vp, _i, _i, _i, _i64, _i, _i, _vp]),

@@ -903,6 +903,32 @@ int cream_mixup_cutmix(float* x, float* y, const int64_t* target, int B, int Cim
 int cream_soft_ce(float* loss_rows, float* dlogits, const void* logits, const float* target, int B, int C, int logits_dtype,
                   float grad_scale, void* stream);
 
+/* ---- TinyViT fast distillation: sparse teacher records (csrc/sparse_distill.hip) ------------------
+ * cream_sparse_ce: the loss of TinyViT/main.py:321-330 — the dense teacher rebuilt from a top-k record, then the
+ * soft-target cross entropy documented at cream_soft_ce — from the SPARSE record, one launch, no B x C target in memory.
+ * Per row b, with index (B x k) int16 and value (B x k) fp16 (the record's fields), 1 <= k <= 128, k < C <= 32768:
+ *   minor        = (1 - sum_j float(value[b,j])) / (C - k)
+ *   t[b,c]       = value[b,j] at c = index[b,j], minor elsewhere
+ *   loss_rows[b] = sum_c t[b,c] (logsumexp(x[b,:]) - x[b,c])                  (the caller takes the mean)
+ *   dlogits[b,c] = (softmax(x[b,:])[c] * sum_c t[b,c] - t[b,c]) * grad_scale   f32, every element stored exactly once
+ * logits (B x C) bf16 or f32 (logits_dtype), rows contiguous (a row of odd length starts at the element's own alignment,
+ * which is all the kernel assumes); softmax statistics in fp32; the terms logsumexp - x[c] are summed as terms.
+ * Indices within a row are distinct by contract (top-k output).  An index outside [0, C) is never dereferenced: its value
+ * counts in `minor` and nowhere else (the host codec rejects such records).
+ * Returns CREAM_ERR_TOO_LARGE for k > 128 or C > 32768, CREAM_ERR_BAD_ARG for k >= C, k < 1, a null or misaligned pointer,
+ * CREAM_ERR_BAD_DTYPE for other logits types — without launching.
+ *
+ * cream_softmax_topk_records: the writer side (TinyViT/save_logits.py:135-158): softmax, top-k largest first, straight into
+ * the record layout.  records (B x (4 + 4k)) bytes, 4-byte aligned: int32 seed, k int16 indices, k fp16 values.
+ * logits (B x C) bf16 or f32, seeds (B) int32, 1 <= k <= 128, k <= C <= 32768.  The ORDER is defined on the logits (softmax is
+ * monotone, logits compare exactly): larger logit first, equal logits by ascending class index — stricter than
+ * torch.topk, which leaves ties open, and equal to it wherever the fp32 probabilities are distinct.  Values are the fp32
+ * softmax rounded to nearest-even fp16; subnormal results are kept.  Error codes as above (k > C is CREAM_ERR_BAD_ARG). */
+int cream_sparse_ce(float* loss_rows, float* dlogits, const void* logits, const int16_t* index, const void* value, int B, int C,
+                    int k, int logits_dtype, float grad_scale, void* stream);
+int cream_softmax_topk_records(void* records, const void* logits, const int32_t* seeds, int B, int C, int k, int logits_dtype,
+                               void* stream);
+
 /* ---- fp32-I/O instantiations (parity mode) -------------------------------------------------------
  * The same operators with fp32 tensors on both sides, for the "within 1e-3 of the reference PyTorch-CPU
  * forward / backward" bar: exact-fp32 matrix-core products (v_mfma_f32_32x32x2_f32; gfx950 has no TF32)
