@@ -70,6 +70,8 @@ SIGNATURES = {
     "cream_token_dwconv3_blocks": (_i, [_vp]),
     "cream_token_dwconv3_fwd": (_i, [_vp, _vp]),
     "cream_token_dwconv3_bwd": (_i, [_vp, _vp]),
+    "cream_cga_attn_check": (_i, [_vp]),
+    "cream_cga_attn_fwd": (_i, [_vp, _vp]),
     "cream_relation_loss_check": (_i, [_vp]),
     "cream_relation_loss_blocks": (_i, [_vp]),
     "cream_relation_loss": (_i, [_vp, _vp]),
@@ -264,6 +266,13 @@ class TokenDwconv3Desc(ctypes.Structure):
     _fields_ = ([(n, _vp) for n in ("x", "w", "bias", "y")] +
                 [(n, _c.c_int32) for n in ("B", "Hs", "Ws", "C", "dtype", "part_blocks")] +
                 [(n, _vp) for n in ("dy", "dx", "part")])
+
+
+class CgaDesc(ctypes.Structure):
+    """struct cream_cga_desc of include/cream_amd.h."""
+    _fields_ = ([("x", _vp)] + [(n, _i64) for n in ("xsb", "xsy", "xsx")] +
+                [(n, _vp) for n in ("wqkv", "bqkv", "dw", "dwb", "ab", "out")] +
+                [(n, _c.c_int32) for n in ("B", "Hs", "Ws", "w", "h", "Cg", "relu")] + [("ks", _c.c_int32 * 4), ("scale", _f)])
 
 
 class RelationSide(ctypes.Structure):

@@ -481,6 +481,40 @@ int cream_token_dwconv3_fwd(const cream_token_dwconv3_desc* d, void* stream);
 /* dx and the partials of dw and dbias from dy and x.  Two launches. */
 int cream_token_dwconv3_bwd(const cream_token_dwconv3_desc* d, void* stream);
 
+/* ---- EfficientViT's cascaded group attention, inference (csrc/cga_attn.hip) ------------------------------------------
+ * What CascadedGroupAttention.forward (EfficientViT/classification/model/efficientvit.py:159-180) computes between its input
+ * and the ReLU in front of `proj`, BatchNorm folded, for every w x w window of the map in one launch.  With Cg = C / h and
+ * x_i the i-th group of Cg channels, head i = 0 .. h - 1 in sequence:
+ *     feat_in_i = x_i (i = 0)  |  feat_{i-1} + x_i
+ *     [q | k | v] = feat_in_i W_i^T + b_i                    q, k: 16 wide, v: Cg wide
+ *     q' = depthwise k_i x k_i convolution of q inside the window (zero padding) + bias
+ *     feat_i = softmax(scale q' k^T + ab_i) v                out[.., i Cg : (i + 1) Cg] = feat_i  (relu: max(feat_i, 0))
+ * Rounding: feat_in, q, k, v, q' and feat_i are bf16 (fp32 accumulation, then bias, then one rounding); logits, softmax and the
+ * row sum fp32; the probabilities enter the last product as bf16(exp(l - max)), the division by the fp32 row sum comes after
+ * it.  The stored pre-ReLU feat_i is the value head i + 1 reads.
+ * Ranges: Cg in {16, 32, .., 112}, 1 <= h <= 4, 1 <= w <= 8, k_i in {1, 3, 5, 7}, Hs and Ws multiples of w.  x, wqkv, bqkv and out
+ * 16-byte aligned, the strides of x multiples of 8 elements with xsx >= h Cg; anything else returns CREAM_ERR_BAD_ARG before
+ * any HIP call.  One workgroup per window (not persistent), no atomics, no scratch. */
+typedef struct cream_cga_desc {
+    const void* x;                  /* bf16, element (b, y, x, c) at b xsb + y xsy + x xsx + c                 */
+    int64_t xsb, xsy, xsx;          /* in elements                                                             */
+    const void* wqkv;               /* bf16 (h, 32 + Cg, KP): rows [q | k | v], KP = Cg rounded up to 32, zeros past Cg */
+    const float* bqkv;              /* (h, 32 + Cg)                                                            */
+    const float* dw;                /* the taps (16, k_i, k_i) of head 0, 1, .. one after the other            */
+    const float* dwb;               /* (h, 16)                                                                 */
+    const float* ab;                /* (h, w^2, w^2): attention_biases[:, attention_bias_idxs]                 */
+    void* out;                      /* bf16 (B, Hs, Ws, h Cg) contiguous                                       */
+    int32_t B, Hs, Ws, w, h, Cg, relu;
+    int32_t ks[4];                  /* k_i                                                                     */
+    float scale;
+} cream_cga_desc;
+
+/* CREAM_OK when cream_cga_attn_fwd would launch for this descriptor, its error code otherwise.  Pure host arithmetic. */
+int cream_cga_attn_check(const cream_cga_desc* d);
+
+/* out from x and the folded operands.  One launch. */
+int cream_cga_attn_fwd(const cream_cga_desc* d, void* stream);
+
 /* ---- the relation losses of the Mini-Swin distillation step (csrc/distill_loss.hip) -------------------------------
  * cal_relation_loss and cal_hidden_relation_loss of MiniViT/Mini-Swin/main.py:39-57 and :66-77, each with the gradient
  * with respect to the student in the same call.  No atomics: one fp32 partial of the (already scaled) loss per workgroup,
