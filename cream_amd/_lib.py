@@ -116,6 +116,14 @@ SIGNATURES = {
     "cream_gelu_bwd_colsum": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp]),
     "cream_scale_cast_colsum": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "cream_grad_finalize": (_i, [_vp, _i, _vp]),
+    "cream_ln_fwd_masked": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp]),
+    "cream_add_ln_fwd_masked": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _f, _vp]),
+    "cream_ln_bwd_masked": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp]),
+    "cream_mask_pack_check": (_i, [_vp, _i]),
+    "cream_mask_pack": (_i, [_vp, _i, _vp]),
+    "cream_mask_grad_ws_floats": (_i64, [_i, _i]),
+    "cream_mask_grad_check": (_i, [_vp, _i]),
+    "cream_mask_grad_finalize": (_i, [_vp, _i, _vp]),
     "cream_gemm_rows_per_colsum_slab": (_i, []),
     "cream_gemm_nt256": (_i, [_i]),
     "cream_gemm_nt8": (_i, [_i]),
@@ -180,6 +188,23 @@ class GradJob(ctypes.Structure):
     _fields_ = [("dst", _vp), ("src", _vp), ("ld", _i64), ("pstride", _i64),
                 ("nparts", _c.c_int32), ("rows", _c.c_int32), ("cols", _c.c_int32),
                 ("interleave", _c.c_int32), ("src_bf16", _c.c_int32), ("overwrite", _c.c_int32)]
+
+MAX_MASK_JOBS = 16
+
+
+class MaskPackJob(ctypes.Structure):
+    """struct cream_mask_pack_job of include/cream_amd.h."""
+    _fields_ = ([(n, _vp) for n in ("w", "r", "c", "mir", "mir_t")] + [(n, _i64) for n in ("ld", "ld_mir", "ld_mir_t")] +
+                [(n, _c.c_int32) for n in ("rows", "cols", "c_group", "reserved")])
+
+
+class MaskGradJob(ctypes.Structure):
+    """struct cream_mask_grad_job of include/cream_amd.h."""
+    _fields_ = ([(n, _vp) for n in ("dst", "src", "w", "r", "c", "dr_out", "dc_out", "ws")] +
+                [(n, _i64) for n in ("ld", "pstride", "ld_w")] +
+                [(n, _c.c_int32) for n in ("nparts", "rows", "cols", "c_group", "src_bf16", "overwrite", "dr_accumulate",
+                                           "dc_accumulate")])
+
 
 class ImageDesc(ctypes.Structure):
     """struct cream_image_desc of include/cream_amd.h."""

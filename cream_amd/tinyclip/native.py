@@ -93,11 +93,10 @@ def supported(transformer, x, attn_mask, causal=False):
     """`causal`: the caller vouches that `attn_mask` is the additive upper-triangular -inf mask (TextEncoder's buffer)."""
     if not len(transformer.resblocks):
         return False
-    if not ((attn_mask is None or causal) and x.is_cuda and x.dim() == 3
-            and torch.is_autocast_enabled('cuda') and torch.get_autocast_dtype('cuda') == torch.bfloat16
+    if not ((attn_mask is None or causal) and x.dim() == 3 and _environment_ok(x)
             and transformer.head_dim == 64 and transformer.width % 8 == 0 and x.shape[1] <= 2048):
         return False
-    if not all(_block_supported(blk) for blk in transformer.resblocks):
+    if not all(_block_supported(blk) and _block_dense(blk, transformer.width) for blk in transformer.resblocks):
         return False
     if torch.is_grad_enabled():
         # the native backward writes a `.grad` for every parameter of every block: a tower with frozen parameters that is
@@ -108,8 +107,24 @@ def supported(transformer, x, attn_mask, causal=False):
     return True
 
 
+def _environment_ok(x):
+    """The input lives on the device and the call is under bf16 autocast."""
+    return x.is_cuda and torch.is_autocast_enabled('cuda') and torch.get_autocast_dtype('cuda') == torch.bfloat16
+
+
+def _block_dense(blk, width):
+    """The actual parameter shapes are those of a dense block of `width`: a tower cut down by `prune()` (a lost branch, inner
+    = 64 H_l != width, per-layer MLP widths around a smaller stream) keeps the composed path."""
+    at, mlp = blk.attn, blk.mlp
+    return (tuple(at.in_proj_weight.shape) == (3 * width, width) and tuple(at.out_proj.weight.shape) == (width, width)
+            and at.num_heads * 64 == width and mlp.c_fc.weight.shape[1] == width and mlp.c_proj.weight.shape[0] == width
+            and tuple(blk.ln_1.weight.shape) == (width,) and tuple(blk.ln_2.weight.shape) == (width,))
+
+
 def _block_supported(blk):
     """Every block is looked at, not the first alone."""
+    if getattr(blk, 'attn', None) is None or getattr(blk, 'mlp', None) is None:
+        return False
     return (isinstance(blk.mlp.gelu, torch.nn.GELU) and getattr(blk.mlp.gelu, 'approximate', 'none') == 'none'
             and isinstance(blk.ln_attn, torch.nn.Identity) and blk.attn.in_proj_weight.dtype == torch.float32
             and blk.mlp.c_fc.weight.shape[0] % 8 == 0)

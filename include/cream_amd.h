@@ -874,6 +874,75 @@ typedef struct cream_grad_job {
 #define CREAM_MAX_GRAD_JOBS 24
 int cream_grad_finalize(const cream_grad_job* jobs, int njobs, void* stream);
 
+/* ---- TinyCLIP's pruning masks folded into the operands (csrc/l0_mask.hip) ------------------------------------------------
+ * TinyCLIP/src/open_clip/l0module.py; model.py:40-68 (masked LayerNorm), :131-136 and :273-282 (hidden_z / heads_z /
+ * intermediate_z on c_proj and out_proj).  With zh (D), zd (H) expanded to 64 columns per head, zi (F):
+ *     Wo' = diag(zh) Wo diag(e(zd)),  bo' = zh * bo,  W2' = diag(zh) W2 diag(zi),  b2' = zh * b2
+ * the masked block is the dense block on these operands with the masked LayerNorm in place of ln_1 / ln_2.
+ *
+ * Masked LayerNorm: the contracts of cream_ln_fwd / cream_add_ln_fwd / cream_ln_bwd with a mask z (E floats, 16-byte aligned):
+ * column c is KEPT iff z[c] != 0, and n_keep is the number of kept columns as the caller counted it (1 <= n_keep <= E;
+ * n_keep <= 0 returns CREAM_ERR_BAD_ARG and launches nothing).  Mean and variance are over the kept columns only, divisor
+ * n_keep — the dropped columns are selected away, not multiplied: whatever they hold, finite or not, never enters a sum.
+ * y is exactly 0 in the dropped columns (n_keep == 1: variance 0, y = beta in the kept column).  xsum is x + scale * res in
+ * EVERY column.  Backward: dy of a dropped column is discarded, the LayerNorm's contribution to dx and the dgamma / dbeta
+ * partials are exactly 0 there, dres passes through in every column, dx_scaled and the third partial row cover every
+ * column as in cream_ln_bwd.  No gradient reaches z (the reference selects by torch.where(hidden_z != 0)). */
+int cream_ln_fwd_masked(void* y, float* mean, float* rstd, const float* x, const float* gamma, const float* beta,
+                        const float* z, int n_keep, int M, int E, float eps, void* stream);
+int cream_add_ln_fwd_masked(float* xsum, void* y, float* mean, float* rstd, const float* x, const void* res,
+                            const float* sample_scale, int rows_per_sample, const float* gamma, const float* beta,
+                            const float* z, int n_keep, int M, int E, float eps, void* stream);
+int cream_ln_bwd_masked(float* dx, void* dx_scaled, float* partial, const void* dy, const float* x, const float* mean,
+                        const float* rstd, const float* gamma, const float* z, int n_keep, const float* dres,
+                        const float* sample_scale, int rows_per_sample, int M, int E, void* stream);
+
+/* Masked operand pack, several tensors per launch (the job table is HOST memory, copied into the launch):
+ *     mir[i * ld_mir + k]     = bf16((w[i * ld + k] * r[i]) * c[k / c_group])        i < rows, k < cols
+ *     mir_t[k * ld_mir_t + i] = the same value
+ * the products in fp32 in this order, rounded once to nearest-even; r == NULL / c == NULL: that factor is absent.  c_group is
+ * 1 (a factor per column) or 64 (a factor per head of 64 columns).  mir or mir_t may be NULL (not both).  A bias b (n) with
+ * its mask is the job rows = 1, cols = n, c = the mask.  cols, ld, ld_mir % 4 == 0; with mir_t also rows, ld_mir_t % 4 == 0;
+ * w 16-byte, the copies 8-byte aligned. */
+typedef struct cream_mask_pack_job {
+    const float* w;
+    const float* r;        /* rows entries or NULL                       */
+    const float* c;        /* cols / c_group entries or NULL             */
+    void *mir, *mir_t;     /* bf16 (rows x cols) / (cols x rows) or NULL */
+    int64_t ld, ld_mir, ld_mir_t;
+    int32_t rows, cols, c_group, reserved;
+} cream_mask_pack_job;
+#define CREAM_MAX_MASK_JOBS 16
+int cream_mask_pack_check(const cream_mask_pack_job* jobs, int njobs);
+int cream_mask_pack(const cream_mask_pack_job* jobs, int njobs, void* stream);
+
+/* Masked gradient finalisation: src holds the partial sums of the gradient of an EFFECTIVE operand W' = diag(r) W diag(c)
+ * (layout, src_bf16 and overwrite as in cream_grad_job; no interleave).  With G = sum_p src[p] in the summation tree of
+ * cream_grad_finalize:
+ *     dst[i * ld + k] (+)= (r[i] * c[k / c_group]) * G[i, k]                          (the gradient of W)
+ *     dr_out[i]       (+)= sum_k (G[i, k] * w[i, k]) * c[k / c_group]                 (the gradient of r; dr_accumulate)
+ *     dc_out[g]       (+)= sum_{k in group g} sum_i (G[i, k] * w[i, k]) * r[i]        (the gradient of c; dc_accumulate)
+ * r / c == NULL: that factor is 1; dr_out / dc_out == NULL: not computed.  A bias is the job rows = 1, cols = n, c = its mask,
+ * dc_out = the mask's gradient.  The matrix is walked in fixed 16 x 64 tiles; a tile's row and column sums go to ws
+ * (cream_mask_grad_ws_floats(rows, cols) floats per job, required with dr_out or dc_out) and a second launch adds them in
+ * ascending tile order: every result is bit-reproducible and independent of the grid (cream_cu_reserve).  Within one call no
+ * two jobs may share dst, dr_out, dc_out or ws (CREAM_ERR_BAD_ARG): every output has one writer.  Host job table. */
+typedef struct cream_mask_grad_job {
+    float* dst;
+    const void* src;
+    const float* w;        /* the fp32 master tensor, row stride ld_w */
+    const float* r;
+    const float* c;
+    float* dr_out;
+    float* dc_out;
+    float* ws;
+    int64_t ld, pstride, ld_w;
+    int32_t nparts, rows, cols, c_group, src_bf16, overwrite, dr_accumulate, dc_accumulate;
+} cream_mask_grad_job;
+int64_t cream_mask_grad_ws_floats(int rows, int cols);
+int cream_mask_grad_check(const cream_mask_grad_job* jobs, int njobs);
+int cream_mask_grad_finalize(const cream_mask_grad_job* jobs, int njobs, void* stream);
+
 /* ---- the uint8 -> normalised float input transform of a batch, on the device (csrc/image_transform.hip) -----------------
  * AutoFormer/lib/datasets.py:189-220 (`build_transform`): eval = Resize(int(256 / 224 * input_size), bicubic) -> CenterCrop ->
  * ToTensor -> Normalize; train = timm's RandomResizedCropAndInterpolation(bicubic) -> RandomHorizontalFlip -> [RandAugment: host
