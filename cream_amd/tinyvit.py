@@ -1,8 +1,8 @@
 """TinyViT — host-side mirror of TinyViT/models/tiny_vit.py (`Conv2d_BN` :28-50, `PatchEmbed` :64-81, `MBConv` :84-122,
 `PatchMerging` :125-151, `ConvLayer` :154-190, `Mlp` :193-213, `Attention` :216-286, `TinyViTBlock` :289-383, `BasicLayer`
 :386-450, `TinyViT` :453-591, the factories :640-704) on the fused window attentions of cream_amd.window_attn (windows up to
-8 x 8) and cream_amd.window_attn_large (9 x 9 .. 14 x 14), and on the token-layout depthwise convolution of
-cream_amd.token_conv.
+8 x 8), cream_amd.window_attn_large (9 x 9 .. 14 x 14) and cream_amd.window_attn_xl (15 x 15 .. 32 x 32: the 384 and 512
+models), and on the token-layout depthwise convolution of cream_amd.token_conv.
 
 Same constructor arguments, parameter and buffer names as the reference (`layers.{i}.blocks.{j}.attn.attention_biases`,
 `...local_conv.c.weight`, `...local_conv.bn.running_mean`, ...; `attention_bias_idxs` is non-persistent), so the published
@@ -17,10 +17,11 @@ TinyViT's attention needs no kernel of its own:
 
 Two paths through `TinyViTBlock.forward`, chosen separately for its two halves:
   * attention, fused — a device tensor under bf16 autocast, `CREAM_IRPE_FUSED` not 0, the map a multiple of the window (the
-    reference would not pad), 32-wide heads and `usable_window` / `usable_large_window` for the expanded table: norm -> qkv on
-    the whole (B, L, C) map -> the strided view -> `window_attention` (w <= 8) or `large_window_attention` (9 <= w <= 14) ->
-    proj; no pad, no partition, no (N, N) map.  Everything else (fp32, CPU, padded maps, windows of 16, 24 and 32) is the
-    reference's arithmetic step by step;
+    reference would not pad), 32-wide heads and `usable_window` / `usable_large_window` / `usable_xl_window` for the expanded
+    table (`TinyViTBlock.attention_route`): norm -> qkv on the whole (B, L, C) map -> the strided view -> `window_attention`
+    (w <= 8), `large_window_attention` (9 <= w <= 14) or `xl_window_attention` (15 <= w <= 32, the shapes measured faster:
+    `window_attn_xl.routed`) -> proj; no pad, no partition, no (N, N) map.  Everything else (fp32, CPU, padded maps, 64-wide
+    heads) is the reference's arithmetic step by step;
   * local convolution, fused — on a device, with or without autocast, when `fused_local_conv` is set and
     `token_conv.usable_token_conv` holds: in training mode the convolution on the token layout, then the block's own
     BatchNorm on (B L, C) samples (same statistics and running updates as the reference's (B, C, H, W)); in eval mode
@@ -36,7 +37,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 import torch.utils.checkpoint as checkpoint
 
-from . import token_conv, window_attn, window_attn_large
+from . import token_conv, window_attn, window_attn_large, window_attn_xl
 from .rpe_attention import DropPath
 
 HEAD_DIM = 32
@@ -249,7 +250,7 @@ class Attention(nn.Module):
         self.attention_biases = nn.Parameter(torch.zeros(num_heads, r0 * r1))
         self.register_buffer('attention_bias_idxs', (off[..., 0] * r1 + off[..., 1]).long(), persistent=False)
         # the index tensors of `expand_offset_bias`, for the windows the fused kernels cover
-        self.fusable = r0 == r1 and r0 <= window_attn_large.MAX_WINDOW and key_dim == HEAD_DIM and self.d == HEAD_DIM
+        self.fusable = r0 == r1 and r0 <= window_attn_xl.MAX_WINDOW and key_dim == HEAD_DIM and self.d == HEAD_DIM
         if self.fusable:
             for name, t in zip(("_expand_src", "_fold_idx", "_fold_valid"), offset_bias_index(r0)):
                 self.register_buffer(name, t.clone(), persistent=False)
@@ -294,6 +295,13 @@ class Attention(nn.Module):
             return 'large'
         return None
 
+    def fused_route(self, dtype, device, table):
+        """`fused_kind`, and 'xl' (window_attn_xl) for the windows of 15 .. 32 that only the streaming kernels cover."""
+        kind = self.fused_kind(dtype, device, table)
+        if kind is None and self.fusable and window_attn_xl.usable_xl_window(dtype, device, HEAD_DIM, self.num_heads, self.resolution[0], table):
+            return 'xl'
+        return kind
+
     def forward_map(self, x, geometry, kind, table):
         """x (B, Hs*Ws, C) of the whole map -> (B, Hs*Ws, C) after proj, through the fused kernels."""
         B, L, _ = x.shape
@@ -301,8 +309,10 @@ class Attention(nn.Module):
         packed = qkv.view(B, L, self.num_heads, 3, HEAD_DIM).permute(0, 1, 3, 2, 4)       # (B, L, 3, H, 32), a view
         if kind == 'small':
             out = window_attn.window_attention(packed, self.scale, table, geometry)
-        else:
+        elif kind == 'large':
             out = window_attn_large.large_window_attention(packed, self.scale, table, geometry)
+        else:
+            out = window_attn_xl.xl_window_attention(packed, self.scale, table, geometry)
         return self.proj(out)
 
     def forward(self, x):
@@ -358,12 +368,22 @@ class TinyViTBlock(nn.Module):
     def attention_kind(self, dtype, device):
         """-> (kind, table) for an input that runs in `dtype` (token_conv.io_dtype) on `device`: 'small' / 'large' and the
         expanded table when the fused attention takes it, else (None, None)."""
+        kind, table = self.attention_route(dtype, device)
+        return (kind, table) if kind in ('small', 'large') else (None, None)
+
+    def attention_route(self, dtype, device):
+        """-> (kind, table) as `attention_kind`, with kind 'xl' for the windows of 15 .. 32 (the 384 and 512 models) that
+        cream_amd.window_attn_xl takes; `window_attention` follows this one.  Of those windows only the shapes that were
+        measured faster than composed are routed (`window_attn_xl.routed`: in ACCEPTED, not in EXCLUDED); any other keeps the
+        composed path it had."""
         H, W = self.input_resolution
         w = self.window_size
         if not self.attn.fusable or torch.device(device).type != 'cuda' or H % w or W % w or dtype != torch.bfloat16:
             return None, None
         table = self.attn.table()
-        kind = self.attn.fused_kind(dtype, device, table)
+        kind = self.attn.fused_route(dtype, device, table)
+        if kind == 'xl' and not window_attn_xl.routed(w, H, W, self.num_heads):
+            kind = None
         return kind, (table if kind is not None else None)
 
     def conv_is_fused(self, dtype, device):
@@ -408,7 +428,7 @@ class TinyViTBlock(nn.Module):
         H, W = self.input_resolution
         B, L, C = x.shape
         w = self.window_size
-        kind, table = self.attention_kind(token_conv.io_dtype(x), x.device)
+        kind, table = self.attention_route(token_conv.io_dtype(x), x.device)
         if kind is not None:
             return self.attn.forward_map(x, (H, W, w, 0, 0), kind, table)
         if H == w and W == w:

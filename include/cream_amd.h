@@ -444,6 +444,50 @@ int cream_window_attn_large_fwd(const cream_window_attn_large_desc* d, void* str
 /* dq, dk, dv, delta and the partials of d table from dout and lse.  Two launches. */
 int cream_window_attn_large_bwd(const cream_window_attn_large_desc* d, void* stream);
 
+/* ---- fused window attention for windows of 15x15 .. 32x32 (csrc/window_attn_xl.hip) ----------------------------------
+ * The attention of a TinyViT block at high resolution (TinyViT/models/tiny_vit.py:216-286, windows of 16, 24 and 32) between
+ * the qkv and proj linears, with the window partition in the addressing:
+ *     S_h = (s q_h) k_h^T + table[rel(i,j), h],  P_h = softmax(S_h),  O_h = P_h v_h.
+ * The conventions of cream_window_attn_large_desc; keys and values stream through LDS instead of staying there.  bf16
+ * operands, fp32 accumulation; head_dim 32, 1 <= H <= 32 independent heads, square windows with 15 <= w <= 32, Hs and Ws
+ * multiples of w, shift == mask_shift == 0 (no shifted window is implemented at these sizes).  Anything else returns
+ * CREAM_ERR_BAD_ARG before any HIP call; B == 0 is a no-op.  NP = w * w rounded up to a multiple of 32.  Nothing of size N^2
+ * per window is written; no global atomics: d table comes as (part_blocks, (2w-1)^2, H) fp32 partials, every entry written
+ * once, which the caller sums over the first axis. */
+typedef struct cream_window_attn_xl_desc {
+    const void *q, *k, *v;          /* bf16; element (b, n, h, :) at ptr[b*sb + n*sn + h*sh]                 */
+    int64_t sb, sn, sh;
+    void* out;                      /* (B, Hs*Ws, H, 32) bf16 (fwd only)                                   */
+    float* lse;                     /* (B * nW, H, NP): log-sum-exp of the logits (fwd: out, bwd: in)       */
+    const float* table;             /* ((2w-1)^2, H) fp32                                                  */
+    int32_t B, H, Hs, Ws, w, shift, mask_shift, head_dim;
+    float scale;
+    int32_t part_blocks;            /* bwd: cream_window_attn_xl_blocks(d), the first axis of `part`        */
+    /* backward only */
+    const void* dout;               /* (B, Hs*Ws, H, 32) bf16                                              */
+    void *dq, *dk, *dv;             /* bf16; element (b, n, h, :) at ptr[b*dsb + n*dsn + h*dsh]             */
+    int64_t dsb, dsn, dsh;
+    float* delta;                   /* (B * nW, H, NP) fp32 out: sum_j P dP of every query                 */
+    float* part;                    /* (part_blocks, cream_window_attn_xl_part_size(H, w)) fp32 out         */
+} cream_window_attn_xl_desc;
+
+/* The argument check of the calls below alone (backward != 0: of cream_window_attn_xl_bwd, except part_blocks' value):
+ * CREAM_OK or the error code.  Pure host arithmetic. */
+int cream_window_attn_xl_check(const cream_window_attn_xl_desc* d, int backward);
+
+/* Floats per partial, (2w-1)^2 H, or CREAM_ERR_BAD_ARG.  Pure host arithmetic. */
+int cream_window_attn_xl_part_size(int H, int w);
+
+/* Partials of d table for this descriptor's shape (B, H, Hs, Ws, w): the persistent grids have this many workgroups per
+ * head (from cream_cu_count(); the data pointers are not looked at), 0 when B == 0, or an error code. */
+int cream_window_attn_xl_blocks(const cream_window_attn_xl_desc* d);
+
+/* out and lse from q, k, v.  One launch. */
+int cream_window_attn_xl_fwd(const cream_window_attn_xl_desc* d, void* stream);
+
+/* dq, dk, dv, delta and the partials of d table from dout and lse.  Two launches. */
+int cream_window_attn_xl_bwd(const cream_window_attn_xl_desc* d, void* stream);
+
 /* ---- depthwise 3 x 3 convolution on the token layout (csrc/token_dwconv.hip) -----------------------------------------
  * The local convolution of a TinyViT block (TinyViT/models/tiny_vit.py:333-335, :374-376) without the transposes to NCHW and
  * back: x (B, Hs*Ws, C) contiguous, token n = i * Ws + j; stride 1, zero padding 1:
