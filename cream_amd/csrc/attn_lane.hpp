@@ -1,6 +1,7 @@
 // attn_lane.hpp — the lane-level helpers shared by the bf16 attention kernels that use the swapped product of
 // attn_common.hpp, where a lane owns ONE token and holds 16 partners of it per 32 x 32 tile (irpe_attn.hip, irpe_attn_x.hip,
-// mini_attn.hip, window_attn.hip, distill_loss.hip).
+// mini_attn.hip, window_attn.hip, distill_loss.hip, and window_attn_large.hip and window_attn_xl.hip through
+// window_attn_rows.hpp, which adds what those two share beyond this file: a pitch and the arithmetic of a tile at that pitch).
 //
 // What belongs here: what one lane (or one wave, for the head exchange) does with registers and pointers it is handed —
 // operand fragments, byte bucket ids, the ordered scatter-add, output rows, the X[h][r4][lane] exchange.  What does not:

@@ -6,6 +6,10 @@
 // T = relative_position_bias_table ((2w-1)^2, H) fp32:
 //     S_h[i,j] = (s q_h,i).k_h,j + T[rel(i,j), h] (+ mask[i,j] in {0, -100})      P_h = softmax_j(S_h)      O_h,i = sum_j P_h[i,j] v_h,j
 //
+// The tile format, the lane's products, logit, log-sum-exp and P, and the host's descriptor check are window_attn_rows.hpp, shared
+// with window_attn_xl.hip (15x15 .. 32x32); this file has what is this family's own: the head's K and V resident in LDS, the
+// shift's geometry, the loops.  The tile bodies of the backward are the same text in both files (window_attn_rows.hpp says why).
+//
 // Geometry: the conventions of window_attn.hip:14-19.  The kernels read the packed projection of the UNSHIFTED, UNPARTITIONED map
 // and write the output in the same token order: local token (iy, ix) of window (wy, wx) is map token
 // ((wy w + iy + shift) mod Hs, (wx w + ix + shift) mod Ws); rel(i,j) = (iy-jy+w-1)(2w-1) + (ix-jx+w-1); the mask compares the region
@@ -47,16 +51,11 @@
 #include <hip/hip_bfloat16.h>
 #include <stdint.h>
 
-#include "attn_lane.hpp"
-#include "cream_amd.h"
-#include "cu_budget.hpp"
+#include "window_attn_rows.hpp"
 
 namespace {
 using namespace cream;
 
-constexpr float LOG2E = 1.4426950408889634f;
-constexpr int KP = 40;                 // pitch (bf16) of the staged rows (16-byte aligned rows, 8-byte aligned for the transposing read)
-constexpr int MAXH = 32;
 constexpr int WMIN = 9, WMAX = 14;
 constexpr int XT = 8;                  // X tiles of launch Q: query tiles wave + 4 round, round = 0, 1
 
@@ -143,35 +142,8 @@ __device__ __forceinline__ void stage_rows(short* dst, const short* base, int64_
         *reinterpret_cast<F*>(dst + row * KP + cc * 8) = x;
     }
 }
-// tile^T (rows = the 32 staged tokens of tile t, column = own token) = staged rows . own^T
-__device__ __forceinline__ f32x16 lds_tile(const short* rows, int t, const F (&own)[2], int lane) {
-    const short* rp = rows + (t * 32 + (lane & 31)) * KP + (lane >> 5) * 8;
-    f32x16 s = {};
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) s = TT::mma(TT::load(rp + ks * 16), own[ks], s);
-    return s;
-}
-// acc^T (32 x own tokens) += tile^T (32 x 32 staged tokens of tile t) . p (32 staged x own), p in accumulator layout
-__device__ __forceinline__ void rows_product(f32x16& acc, const short* rows, int t, const f32x16& p, int lane) {
-#pragma unroll
-    for (int s2 = 0; s2 < 2; ++s2) acc = TT::mma(load_perm_tr<KP>(rows + t * 32 * KP, 0, s2, lane), TT::from_acc(p, s2), acc);
-}
-// logits of (own query, keys acc_row(r, g) of tile t): the product + table + mask; keys past N: -inf
-__device__ __forceinline__ void add_bias(f32x16& S, const Ctx& c, const Args& a, int t, int qkc, int qreg, int g) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int j = t * 32 + acc_row(r, g);
-        const float s = S[r] + c.tl[qkc - c.kc[j]] + (c.reg[j] != qreg ? -100.f : 0.f);
-        S[r] = j < a.N ? s : -INFINITY;
-    }
-}
-__device__ __forceinline__ void load_own(F (&f)[2], const short* row, int g, float s, bool scale_it) {
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-        f[ks] = TT::load(row + ks * 16 + g * 8);
-        if (scale_it) f[ks] = scaled(f[ks], s);
-    }
-}
+// the 32 staged rows of tile t
+__device__ __forceinline__ const short* tile_of(const short* rows, int t) { return rows + t * 32 * KP; }
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // forward
@@ -199,33 +171,25 @@ __global__ __launch_bounds__(256) void window_attn_large_fwd_kernel(const Args a
             // ---- pass 1: the row's log-sum-exp (tile 0 has 16 real keys for both lane groups, so m is finite after it) ----------
             float m = -INFINITY, l = 0.f;
             for (int t = 0; t < a.NT; ++t) {
-                f32x16 S = lds_tile(c.ra, t, qs, lane);
-                add_bias(S, c, a, t, qkc, qreg, g);
-                float mt = S[0];
-#pragma unroll
-                for (int r = 1; r < 16; ++r) mt = fmaxf(mt, S[r]);
-                const float mn = fmaxf(m, mt);
+                f32x16 S = lds_tile(c.ra, qs, lane, t * 32);
+                add_bias<true>(S, c.tl, c.kc, c.reg, t, qkc, qreg, a.N, g);
+                const float mn = fmaxf(m, tile_max(S));
                 float sum = 0.f;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) sum += __builtin_amdgcn_exp2f((S[r] - mn) * LOG2E);
                 l = l * __builtin_amdgcn_exp2f((m - mn) * LOG2E) + sum;
                 m = mn;
             }
-            // the two lanes of a query: (m0, l0) of lane group 0 first in both, so that both hold the same bits
             const float mx = __shfl_xor(m, 32), lx = __shfl_xor(l, 32);
-            const float m0 = g == 0 ? m : mx, l0 = g == 0 ? l : lx, m1 = g == 0 ? mx : m, l1 = g == 0 ? lx : l;
-            const float mm = fmaxf(m0, m1);
-            const float ll = l0 * __builtin_amdgcn_exp2f((m0 - mm) * LOG2E) + l1 * __builtin_amdgcn_exp2f((m1 - mm) * LOG2E);
-            const float lse = mm + __logf(ll);
+            const float lse = pair_lse(m, l, mx, lx, g);
             if (g == 0) a.lse[((int64_t)win * a.H + h) * a.NP + qi] = lse;
             // ---- pass 2: O = P V with P = exp(S - lse) ---------------------------------------------------------------------------
             f32x16 O = {};
             for (int t = 0; t < a.NT; ++t) {
-                f32x16 S = lds_tile(c.ra, t, qs, lane);
-                add_bias(S, c, a, t, qkc, qreg, g);
-#pragma unroll
-                for (int r = 0; r < 16; ++r) S[r] = __builtin_amdgcn_exp2f((S[r] - lse) * LOG2E);            // -inf -> 0
-                rows_product(O, c.rb, t, S, lane);
+                f32x16 S = lds_tile(c.ra, qs, lane, t * 32);
+                add_bias<true>(S, c.tl, c.kc, c.reg, t, qkc, qreg, a.N, g);
+                p_tile(S, lse);
+                rows_product(O, tile_of(c.rb, t), S, lane);
             }
             if (qi < a.N) store_row(a.out + (((int64_t)b * a.L + qtok) * a.H + h) * 32, O, g, 1.f);
         }
@@ -271,9 +235,9 @@ __global__ __launch_bounds__(256) void window_attn_large_bwd_q_kernel(const Args
                 lse[rd] = a.lse[((int64_t)win * a.H + h) * a.NP + qi];
                 float d0 = 0.f, d1 = 0.f;
                 for (int t = 0; t < a.NT; ++t) {
-                    f32x16 S = lds_tile(c.ra, t, qs[rd], lane);
-                    add_bias(S, c, a, t, qkc[rd], qreg[rd], g);
-                    const f32x16 D = lds_tile(c.rb, t, dof[rd], lane);
+                    f32x16 S = lds_tile(c.ra, qs[rd], lane, t * 32);
+                    add_bias<true>(S, c.tl, c.kc, c.reg, t, qkc[rd], qreg[rd], a.N, g);
+                    const f32x16 D = lds_tile(c.rb, dof[rd], lane, t * 32);
 #pragma unroll
                     for (int r = 0; r < 16; r += 2) {
                         d0 = __builtin_fmaf(qi < a.N ? __builtin_amdgcn_exp2f((S[r] - lse[rd]) * LOG2E) : 0.f, D[r], d0);
@@ -297,15 +261,15 @@ __global__ __launch_bounds__(256) void window_attn_large_bwd_q_kernel(const Args
                 U[0] = f32x16{};
                 if (qt < a.NT) {
                     const bool qok = qt * 32 + c32 < a.N;
-                    f32x16 S = lds_tile(c.ra, t, qs[rd], lane);
-                    add_bias(S, c, a, t, qkc[rd], qreg[rd], g);
-                    const f32x16 D = lds_tile(c.rb, t, dof[rd], lane);
+                    f32x16 S = lds_tile(c.ra, qs[rd], lane, t * 32);
+                    add_bias<true>(S, c.tl, c.kc, c.reg, t, qkc[rd], qreg[rd], a.N, g);
+                    const f32x16 D = lds_tile(c.rb, dof[rd], lane, t * 32);
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
                         const float p = qok ? __builtin_amdgcn_exp2f((S[r] - lse[rd]) * LOG2E) : 0.f;
                         U[0][r] = p * (D[r] - dl[rd]);
                     }
-                    rows_product(dq[rd], c.ra, t, U[0], lane);
+                    rows_product(dq[rd], tile_of(c.ra, t), U[0], lane);
                 }
                 xchg_put<1>(c.X + rd * 4 * 1024, U, 0, 4, wave, lane);         // tile qt = wave + 4 rd; barriers on both sides
             }
@@ -316,7 +280,6 @@ __global__ __launch_bounds__(256) void window_attn_large_bwd_q_kernel(const Args
                 const int off = dy * a.w + dx;                                  // i - j
                 const int lo = max(0, t * 32 + off), hi = min(a.N, t * 32 + 32 + off);
                 if (lo >= hi) continue;
-                // rows iy with the key row iy - dy inside the window, columns ix with ix - dx inside it: only real pairs are visited
                 const int y0 = max(max(0, dy), lo / a.w), y1 = min(min(a.w, a.w + dy), (hi - 1) / a.w + 1);
                 const int x0 = max(0, dx), x1 = min(a.w, a.w + dx);
                 float sum = 0.f;
@@ -374,18 +337,18 @@ __global__ __launch_bounds__(256) void window_attn_large_bwd_kv_kernel(const Arg
             load_own(vf, a.v + (int64_t)b * a.sb + (int64_t)ktok * a.sn + (int64_t)h * a.sh, g, 1.f, false);
             f32x16 dk = {}, dv = {};
             for (int t = 0; t < a.NT; ++t) {
-                f32x16 P = lds_tile(c.ra, t, kf, lane);                        // rows: queries of tile t, column: own key
+                f32x16 P = lds_tile(c.ra, kf, lane, t * 32);                   // rows: queries of tile t, column: own key
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int i = t * 32 + acc_row(r, g);
                     const float s = P[r] + c.tl[c.kc[i] + kkc] + (c.reg[i] != kreg ? -100.f : 0.f);
                     P[r] = (kok && i < a.N) ? __builtin_amdgcn_exp2f((s - c.lse_s[i]) * LOG2E) : 0.f;
                 }
-                rows_product(dv, c.rb, t, P, lane);                             // dv^T += dO^T P
-                f32x16 D = lds_tile(c.rb, t, vf, lane);                         // dP
+                rows_product(dv, tile_of(c.rb, t), P, lane);                    // dv^T += dO^T P
+                f32x16 D = lds_tile(c.rb, vf, lane, t * 32);                    // dP
 #pragma unroll
                 for (int r = 0; r < 16; ++r) D[r] = P[r] * (D[r] - c.dl_s[t * 32 + acc_row(r, g)]);
-                rows_product(dk, c.ra, t, D, lane);                             // dk^T += (s q)^T dS
+                rows_product(dk, tile_of(c.ra, t), D, lane);                    // dk^T += (s q)^T dS
             }
             if (kok) {
                 store_row(a.dk + (int64_t)b * a.dsb + (int64_t)ktok * a.dsn + (int64_t)h * a.dsh, dk, g, 1.f);
@@ -396,57 +359,6 @@ __global__ __launch_bounds__(256) void window_attn_large_bwd_kv_kernel(const Arg
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------------------
-// window lanes per head of the persistent grids: launch Q's carve-up (the largest) sizes all three, so that one partial count
-// describes the descriptor
-int lanes_for(const Args& a) {
-    const int lds = Lds(a.NP, a.NU, true).total;
-    const int per_cu = 160 * 1024 / lds < 4 ? 160 * 1024 / lds : 4;
-    const int cap = cu_count() * per_cu / a.H;
-    const int lanes = cap < 1 ? 1 : cap;
-    return a.nwin < lanes ? a.nwin : lanes;
-}
-template <typename K> int launch(K kern, const Args& a, int blocks, int lds, hipStream_t st) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-        return CREAM_ERR_LAUNCH;
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), (size_t)lds, st, a);
-    return hipGetLastError() == hipSuccess ? CREAM_OK : CREAM_ERR_LAUNCH;
-}
-int run(const Args& a, bool bwd, int lanes, hipStream_t st) {
-    const int lds = Lds(a.NP, a.NU, false).total, ldsq = Lds(a.NP, a.NU, true).total;
-    if (!bwd) return launch(window_attn_large_fwd_kernel, a, lanes * a.H, lds, st);
-    const int rc = launch(window_attn_large_bwd_q_kernel, a, lanes * a.H, ldsq, st);
-    if (rc) return rc;
-    return launch(window_attn_large_bwd_kv_kernel, a, lanes * a.H, lds, st);
-}
-
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-bool aligned8(const void* p) { return ((uintptr_t)p & 7) == 0; }
-bool aligned4(const void* p) { return ((uintptr_t)p & 3) == 0; }
-
-// the shape alone (what sizes the grid and the partials)
-int check_shape(const cream_window_attn_large_desc* d) {
-    if (!d) return CREAM_ERR_BAD_ARG;
-    if (d->head_dim != 32 || d->B < 0 || d->H < 1 || d->H > MAXH) return CREAM_ERR_BAD_ARG;
-    if (d->w < WMIN || d->w > WMAX || d->Hs < d->w || d->Ws < d->w || d->Hs % d->w || d->Ws % d->w) return CREAM_ERR_BAD_ARG;
-    if (d->shift < 0 || d->shift >= d->w || d->mask_shift < 0 || d->mask_shift >= d->w) return CREAM_ERR_BAD_ARG;
-    if ((int64_t)d->B * d->Hs * d->Ws > (int64_t)1 << 30) return CREAM_ERR_TOO_LARGE;
-    return CREAM_OK;
-}
-
-int check(const cream_window_attn_large_desc* d, bool bwd) {
-    if (!d || !d->q || !d->k || !d->v || !d->lse || !d->table || (!bwd && !d->out)) return CREAM_ERR_BAD_ARG;
-    if (const int rc = check_shape(d)) return rc;
-    if (d->sn % 8 || d->sh % 8 || d->sb % 8 || !aligned16(d->q) || !aligned16(d->k) || !aligned16(d->v) || (!bwd && !aligned8(d->out)))
-        return CREAM_ERR_BAD_ARG;
-    if (!aligned4(d->lse) || !aligned4(d->table)) return CREAM_ERR_BAD_ARG;
-    if (bwd) {
-        if (!d->dout || !d->dq || !d->dk || !d->dv || !d->delta || !d->part || d->part_blocks < 1) return CREAM_ERR_BAD_ARG;
-        if (d->dsn % 4 || d->dsh % 4 || d->dsb % 4 || !aligned16(d->dout)) return CREAM_ERR_BAD_ARG;
-        if (!aligned8(d->dq) || !aligned8(d->dk) || !aligned8(d->dv) || !aligned4(d->delta) || !aligned4(d->part)) return CREAM_ERR_BAD_ARG;
-    }
-    return CREAM_OK;
-}
-
 Args to_args(const cream_window_attn_large_desc* d) {
     Args a{};
     a.q = (const short*)d->q; a.k = (const short*)d->k; a.v = (const short*)d->v;
@@ -463,45 +375,34 @@ Args to_args(const cream_window_attn_large_desc* d) {
     return a;
 }
 
+// window lanes per head of the persistent grids
+int lanes_of(const Args& a) { return lanes_for(Lds(a.NP, a.NU, true).total, a.nwin, a.H); }
+
+// the argument check, then the launches
+int run(const cream_window_attn_large_desc* d, bool bwd, void* stream) {
+    if (const int rc = check(d, bwd, WMIN, WMAX, true)) return rc;
+    if (d->B == 0) return CREAM_OK;
+    const Args a = to_args(d);
+    const int lanes = lanes_of(a), lds = Lds(a.NP, a.NU, false).total, ldsq = Lds(a.NP, a.NU, true).total;
+    const hipStream_t st = (hipStream_t)stream;
+    if (!bwd) return launch(window_attn_large_fwd_kernel, a, lanes * a.H, lds, st);
+    if (d->part_blocks != lanes) return CREAM_ERR_BAD_ARG;
+    if (const int rc = launch(window_attn_large_bwd_q_kernel, a, lanes * a.H, ldsq, st)) return rc;
+    return launch(window_attn_large_bwd_kv_kernel, a, lanes * a.H, lds, st);
+}
+
 }  // namespace
 
 extern "C" {
 
-int cream_window_attn_large_check(const cream_window_attn_large_desc* d, int backward) { return check(d, backward != 0); }
-
-int cream_window_attn_large_part_size(int H, int w)
-{
-    if (H < 1 || H > MAXH || w < WMIN || w > WMAX) return CREAM_ERR_BAD_ARG;
-    return (2 * w - 1) * (2 * w - 1) * H;
-}
-
+int cream_window_attn_large_check(const cream_window_attn_large_desc* d, int backward) { return check(d, backward != 0, WMIN, WMAX, true); }
+int cream_window_attn_large_part_size(int H, int w) { return part_size(H, w, WMIN, WMAX); }
 int cream_window_attn_large_blocks(const cream_window_attn_large_desc* d)
 {
-    const int rc = check_shape(d);
-    if (rc) return rc;
-    const Args a = to_args(d);
-    if (a.nwin == 0) return 0;
-    return lanes_for(a);
+    const int rc = check_shape(d, WMIN, WMAX, true);
+    return rc ? rc : d->B == 0 ? 0 : lanes_of(to_args(d));
 }
-
-int cream_window_attn_large_fwd(const cream_window_attn_large_desc* d, void* stream)
-{
-    const int rc = check(d, false);
-    if (rc) return rc;
-    if (d->B == 0) return CREAM_OK;
-    const Args a = to_args(d);
-    return run(a, false, lanes_for(a), (hipStream_t)stream);
-}
-
-int cream_window_attn_large_bwd(const cream_window_attn_large_desc* d, void* stream)
-{
-    const int rc = check(d, true);
-    if (rc) return rc;
-    if (d->B == 0) return CREAM_OK;
-    const Args a = to_args(d);
-    const int lanes = lanes_for(a);
-    if (d->part_blocks != lanes) return CREAM_ERR_BAD_ARG;
-    return run(a, true, lanes, (hipStream_t)stream);
-}
+int cream_window_attn_large_fwd(const cream_window_attn_large_desc* d, void* stream) { return run(d, false, stream); }
+int cream_window_attn_large_bwd(const cream_window_attn_large_desc* d, void* stream) { return run(d, true, stream); }
 
 }  // extern "C"

@@ -4,7 +4,10 @@
 //
 // Semantics per window of N tokens, s = scale, T = the ((2w-1)^2, H) fp32 relative-position table:
 //     S_h[i,j] = (s q_h,i).k_h,j + T[rel(i,j), h]      P_h = softmax_j(S_h)      O_h,i = sum_j P_h[i,j] v_h,j
-// Geometry: the conventions of window_attn_large.hip with shift = mask_shift = 0.  The kernels read the packed projection of the
+// The tile format, the lane's products, logit, log-sum-exp and P, and the host's descriptor check are window_attn_rows.hpp, shared
+// with window_attn_large.hip (9x9 .. 14x14); this file has what is this family's own: the chunked, double-buffered stream, the
+// candidate set of dT, the loops.  The tile bodies of the backward are the same text in both files (window_attn_rows.hpp says why).
+// Geometry: that of window_attn_large.hip's header with shift = mask_shift = 0.  The kernels read the packed projection of the
 // UNPARTITIONED map and write the output in the same token order: local token (iy, ix) of window (wy, wx) is map token
 // (wy w + iy, wx w + ix); rel(i,j) = (iy-jy+w-1)(2w-1) + (ix-jx+w-1).
 //
@@ -17,7 +20,7 @@
 // life: workgroup b has head b mod H and walks the items b / H, b / H + G / H, ... of that head (G = the persistent grid, a
 // multiple of H), so that its share of the table and of dT is one column.  Waves exchange nothing in the forward and in launch K.
 //
-// Softmax: TWO PASSES over the streamed keys, as in the sibling.  Pass 1 streams K alone and keeps a running (max, sum) per lane,
+// Softmax: TWO PASSES over the streamed keys, as in window_attn_large.hip.  Pass 1 streams K alone and keeps a running (max, sum) per lane,
 // pass 2 streams K and V and multiplies P = exp(S - lse) into V; the backward's P = exp(S - lse) is then the forward's P bit for
 // bit, and no O is rescaled.  The second stream of K is LDS and L2 traffic (a head's K of one window is at most 64 KB and is
 // read by the 8 items of the window), not HBM.  Keys past N are staged as zero rows and have S = -inf in pass 1 and P = 0 in
@@ -48,16 +51,11 @@
 #include <hip/hip_bfloat16.h>
 #include <stdint.h>
 
-#include "attn_lane.hpp"
-#include "cream_amd.h"
-#include "cu_budget.hpp"
+#include "window_attn_rows.hpp"
 
 namespace {
 using namespace cream;
 
-constexpr float LOG2E = 1.4426950408889634f;
-constexpr int KP = 40;                 // pitch (bf16) of the staged rows (16-byte aligned rows, 8-byte aligned for the transposing read)
-constexpr int MAXH = 32;
 constexpr int WMIN = 15, WMAX = 32;
 constexpr int CT = 2;                  // 32-row tiles per streamed chunk
 constexpr int CR = CT * 32;            // rows per chunk: 256 threads x one 16-byte piece per operand
@@ -169,36 +167,6 @@ __device__ __forceinline__ void stream(const short* pa, int64_t rsa, const short
     }
 }
 
-// tile^T (rows = the 32 staged tokens of the tile, column = own token) = staged rows . own^T
-__device__ __forceinline__ f32x16 lds_tile(const short* rows, const F (&own)[2], int lane) {
-    const short* rp = rows + (lane & 31) * KP + (lane >> 5) * 8;
-    f32x16 s = {};
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) s = TT::mma(TT::load(rp + ks * 16), own[ks], s);
-    return s;
-}
-// acc^T (32 x own tokens) += tile^T (32 x 32 staged tokens) . p (32 staged x own), p in accumulator layout
-__device__ __forceinline__ void rows_product(f32x16& acc, const short* rows, const f32x16& p, int lane) {
-#pragma unroll
-    for (int s2 = 0; s2 < 2; ++s2) acc = TT::mma(load_perm_tr<KP>(rows, 0, s2, lane), TT::from_acc(p, s2), acc);
-}
-// logits of (own query, keys acc_row(r, g) of tile t): the product + table; keys past N: -inf
-__device__ __forceinline__ void add_bias(f32x16& S, const Ctx& c, const Args& a, int t, int qkc, int g) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int j = t * 32 + acc_row(r, g);
-        const float s = S[r] + c.tl[qkc - c.kc[j]];
-        S[r] = j < a.N ? s : -INFINITY;
-    }
-}
-__device__ __forceinline__ void load_own(F (&f)[2], const short* row, int g, float s, bool scale_it) {
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-        f[ks] = TT::load(row + ks * 16 + g * 8);
-        if (scale_it) f[ks] = scaled(f[ks], s);
-    }
-}
-
 // ---------------------------------------------------------------------------------------------------------------------------
 // forward
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -227,25 +195,18 @@ __global__ __launch_bounds__(256) void window_attn_xl_fwd_kernel(const Args a) {
         stream<false>(kb, a.sn, kb, a.sn, c, a, false, [&](int t, const short* rk, const short*) {
             if (!active) return;
             f32x16 S = lds_tile(rk, qs, lane);
-            add_bias(S, c, a, t, qkc, g);
-            float mt = S[0];
-#pragma unroll
-            for (int r = 1; r < 16; ++r) mt = fmaxf(mt, S[r]);
-            const float mn = fmaxf(m, mt);
+            add_bias<false>(S, c.tl, c.kc, nullptr, t, qkc, 0, a.N, g);
+            const float mn = fmaxf(m, tile_max(S));
             float sum = 0.f;
 #pragma unroll
             for (int r = 0; r < 16; ++r) sum += __builtin_amdgcn_exp2f((S[r] - mn) * LOG2E);
             l = l * __builtin_amdgcn_exp2f((m - mn) * LOG2E) + sum;
             m = mn;
         });
-        // the two lanes of a query: (m0, l0) of lane group 0 first in both, so that both hold the same bits
         float lse = 0.f;
         if (active) {
             const float mx = __shfl_xor(m, 32), lx = __shfl_xor(l, 32);
-            const float m0 = g == 0 ? m : mx, l0 = g == 0 ? l : lx, m1 = g == 0 ? mx : m, l1 = g == 0 ? lx : l;
-            const float mm = fmaxf(m0, m1);
-            const float ll = l0 * __builtin_amdgcn_exp2f((m0 - mm) * LOG2E) + l1 * __builtin_amdgcn_exp2f((m1 - mm) * LOG2E);
-            lse = mm + __logf(ll);
+            lse = pair_lse(m, l, mx, lx, g);
             if (g == 0) a.lse[((int64_t)win * a.H + h) * a.NP + qi] = lse;
         }
         // ---- pass 2: O = P V with P = exp(S - lse) -------------------------------------------------------------------------------
@@ -253,9 +214,8 @@ __global__ __launch_bounds__(256) void window_attn_xl_fwd_kernel(const Args a) {
         stream<true>(kb, a.sn, vb, a.sn, c, a, false, [&](int t, const short* rk, const short* rv) {
             if (!active) return;
             f32x16 S = lds_tile(rk, qs, lane);
-            add_bias(S, c, a, t, qkc, g);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) S[r] = __builtin_amdgcn_exp2f((S[r] - lse) * LOG2E);                // -inf -> 0
+            add_bias<false>(S, c.tl, c.kc, nullptr, t, qkc, 0, a.N, g);
+            p_tile(S, lse);
             rows_product(O, rv, S, lane);
         });
         if (active && qi < a.N) store_row(a.out + (((int64_t)b * a.L + qtok) * a.H + h) * 32, O, g, 1.f);
@@ -296,7 +256,7 @@ __global__ __launch_bounds__(256) void window_attn_xl_bwd_q_kernel(const Args a)
         stream<true>(kb, a.sn, vb, a.sn, c, a, false, [&](int t, const short* rk, const short* rv) {
             if (!active) return;
             f32x16 S = lds_tile(rk, qs, lane);
-            add_bias(S, c, a, t, qkc, g);
+            add_bias<false>(S, c.tl, c.kc, nullptr, t, qkc, 0, a.N, g);
             const f32x16 D = lds_tile(rv, dof, lane);
 #pragma unroll
             for (int r = 0; r < 16; r += 2) {
@@ -314,7 +274,7 @@ __global__ __launch_bounds__(256) void window_attn_xl_bwd_q_kernel(const Args a)
             U[0] = f32x16{};
             if (active) {
                 f32x16 S = lds_tile(rk, qs, lane);
-                add_bias(S, c, a, t, qkc, g);
+                add_bias<false>(S, c.tl, c.kc, nullptr, t, qkc, 0, a.N, g);
                 const f32x16 D = lds_tile(rv, dof, lane);
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
@@ -337,7 +297,6 @@ __global__ __launch_bounds__(256) void window_attn_xl_bwd_q_kernel(const Args a)
                 const int u = (dy + a.w - 1) * W2 + dx + a.w - 1;
                 const int lo = max(q0, t * 32 + off), hi = min(q1, t * 32 + 32 + off);
                 if (lo >= hi) continue;
-                // rows iy with the key row iy - dy inside the window, columns ix with ix - dx inside it: only real pairs are visited
                 const int y0 = max(max(0, dy), lo / a.w), y1 = min(min(a.w, a.w + dy), (hi - 1) / a.w + 1);
                 const int x0 = max(0, dx), x1 = min(a.w, a.w + dx);
                 float sum = 0.f;
@@ -411,56 +370,6 @@ __global__ __launch_bounds__(256) void window_attn_xl_bwd_kv_kernel(const Args a
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------------------
-// item lanes per head of the persistent grids: launch Q's carve-up (the largest) sizes all three, so that one partial count
-// describes the descriptor
-int lanes_for(const Args& a) {
-    const int lds = Lds(a.NP, a.NU, BQ).total;
-    const int per_cu = 160 * 1024 / lds < 4 ? 160 * 1024 / lds : 4;
-    const int cap = cu_count() * per_cu / a.H;
-    const int lanes = cap < 1 ? 1 : cap;
-    return a.nitems < lanes ? a.nitems : lanes;
-}
-template <typename K> int launch(K kern, const Args& a, int blocks, int lds, hipStream_t st) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-        return CREAM_ERR_LAUNCH;
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), (size_t)lds, st, a);
-    return hipGetLastError() == hipSuccess ? CREAM_OK : CREAM_ERR_LAUNCH;
-}
-int run(const Args& a, bool bwd, int lanes, hipStream_t st) {
-    if (!bwd) return launch(window_attn_xl_fwd_kernel, a, lanes * a.H, Lds(a.NP, a.NU, FWD).total, st);
-    const int rc = launch(window_attn_xl_bwd_q_kernel, a, lanes * a.H, Lds(a.NP, a.NU, BQ).total, st);
-    if (rc) return rc;
-    return launch(window_attn_xl_bwd_kv_kernel, a, lanes * a.H, Lds(a.NP, a.NU, BK).total, st);
-}
-
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-bool aligned8(const void* p) { return ((uintptr_t)p & 7) == 0; }
-bool aligned4(const void* p) { return ((uintptr_t)p & 3) == 0; }
-
-// the shape alone (what sizes the grid and the partials)
-int check_shape(const cream_window_attn_xl_desc* d) {
-    if (!d) return CREAM_ERR_BAD_ARG;
-    if (d->head_dim != 32 || d->B < 0 || d->H < 1 || d->H > MAXH) return CREAM_ERR_BAD_ARG;
-    if (d->w < WMIN || d->w > WMAX || d->Hs < d->w || d->Ws < d->w || d->Hs % d->w || d->Ws % d->w) return CREAM_ERR_BAD_ARG;
-    if (d->shift != 0 || d->mask_shift != 0) return CREAM_ERR_BAD_ARG;        // not implemented at these sizes
-    if ((int64_t)d->B * d->Hs * d->Ws > (int64_t)1 << 30) return CREAM_ERR_TOO_LARGE;
-    return CREAM_OK;
-}
-
-int check(const cream_window_attn_xl_desc* d, bool bwd) {
-    if (!d || !d->q || !d->k || !d->v || !d->lse || !d->table || (!bwd && !d->out)) return CREAM_ERR_BAD_ARG;
-    if (const int rc = check_shape(d)) return rc;
-    if (d->sn % 8 || d->sh % 8 || d->sb % 8 || !aligned16(d->q) || !aligned16(d->k) || !aligned16(d->v) || (!bwd && !aligned8(d->out)))
-        return CREAM_ERR_BAD_ARG;
-    if (!aligned4(d->lse) || !aligned4(d->table)) return CREAM_ERR_BAD_ARG;
-    if (bwd) {
-        if (!d->dout || !d->dq || !d->dk || !d->dv || !d->delta || !d->part || d->part_blocks < 1) return CREAM_ERR_BAD_ARG;
-        if (d->dsn % 4 || d->dsh % 4 || d->dsb % 4 || !aligned16(d->dout)) return CREAM_ERR_BAD_ARG;
-        if (!aligned8(d->dq) || !aligned8(d->dk) || !aligned8(d->dv) || !aligned4(d->delta) || !aligned4(d->part)) return CREAM_ERR_BAD_ARG;
-    }
-    return CREAM_OK;
-}
-
 Args to_args(const cream_window_attn_xl_desc* d) {
     Args a{};
     a.q = (const short*)d->q; a.k = (const short*)d->k; a.v = (const short*)d->v;
@@ -478,45 +387,34 @@ Args to_args(const cream_window_attn_xl_desc* d) {
     return a;
 }
 
+// item lanes per head of the persistent grids
+int lanes_of(const Args& a) { return lanes_for(Lds(a.NP, a.NU, BQ).total, a.nitems, a.H); }
+
+// the argument check, then the launches
+int run(const cream_window_attn_xl_desc* d, bool bwd, void* stream) {
+    if (const int rc = check(d, bwd, WMIN, WMAX, false)) return rc;       // no shifted window is implemented at these sizes
+    if (d->B == 0) return CREAM_OK;
+    const Args a = to_args(d);
+    const int lanes = lanes_of(a);
+    const hipStream_t st = (hipStream_t)stream;
+    if (!bwd) return launch(window_attn_xl_fwd_kernel, a, lanes * a.H, Lds(a.NP, a.NU, FWD).total, st);
+    if (d->part_blocks != lanes) return CREAM_ERR_BAD_ARG;
+    if (const int rc = launch(window_attn_xl_bwd_q_kernel, a, lanes * a.H, Lds(a.NP, a.NU, BQ).total, st)) return rc;
+    return launch(window_attn_xl_bwd_kv_kernel, a, lanes * a.H, Lds(a.NP, a.NU, BK).total, st);
+}
+
 }  // namespace
 
 extern "C" {
 
-int cream_window_attn_xl_check(const cream_window_attn_xl_desc* d, int backward) { return check(d, backward != 0); }
-
-int cream_window_attn_xl_part_size(int H, int w)
-{
-    if (H < 1 || H > MAXH || w < WMIN || w > WMAX) return CREAM_ERR_BAD_ARG;
-    return (2 * w - 1) * (2 * w - 1) * H;
-}
-
+int cream_window_attn_xl_check(const cream_window_attn_xl_desc* d, int backward) { return check(d, backward != 0, WMIN, WMAX, false); }
+int cream_window_attn_xl_part_size(int H, int w) { return part_size(H, w, WMIN, WMAX); }
 int cream_window_attn_xl_blocks(const cream_window_attn_xl_desc* d)
 {
-    const int rc = check_shape(d);
-    if (rc) return rc;
-    const Args a = to_args(d);
-    if (a.nwin == 0) return 0;
-    return lanes_for(a);
+    const int rc = check_shape(d, WMIN, WMAX, false);
+    return rc ? rc : d->B == 0 ? 0 : lanes_of(to_args(d));
 }
-
-int cream_window_attn_xl_fwd(const cream_window_attn_xl_desc* d, void* stream)
-{
-    const int rc = check(d, false);
-    if (rc) return rc;
-    if (d->B == 0) return CREAM_OK;
-    const Args a = to_args(d);
-    return run(a, false, lanes_for(a), (hipStream_t)stream);
-}
-
-int cream_window_attn_xl_bwd(const cream_window_attn_xl_desc* d, void* stream)
-{
-    const int rc = check(d, true);
-    if (rc) return rc;
-    if (d->B == 0) return CREAM_OK;
-    const Args a = to_args(d);
-    const int lanes = lanes_for(a);
-    if (d->part_blocks != lanes) return CREAM_ERR_BAD_ARG;
-    return run(a, true, lanes, (hipStream_t)stream);
-}
+int cream_window_attn_xl_fwd(const cream_window_attn_xl_desc* d, void* stream) { return run(d, false, stream); }
+int cream_window_attn_xl_bwd(const cream_window_attn_xl_desc* d, void* stream) { return run(d, true, stream); }
 
 }  // extern "C"

@@ -15,17 +15,13 @@ with the other fused attentions.  `ACCEPTED` holds the (w, Hs, Ws, H) shapes tha
 `EXCLUDED` those that were measured and did not (profiles/NOTES_window_attention_xl.md); a caller that routes by default asks
 `routed(...)`, so an unmeasured shape keeps the path it had.
 """
-import ctypes
-import os
+from . import _lib, _window_rows
+from ._window_rows import HEAD_DIM, MAX_HEADS, padded_tokens  # noqa: F401  (public names of this module)
 
-import torch
-
-from . import _lib, timing
-
-MAX_HEADS = 32
 MIN_WINDOW = 15
 MAX_WINDOW = 32
-HEAD_DIM = 32
+
+_family = _window_rows.Family("window_attn_xl", _lib.WindowAttnXlDesc, MIN_WINDOW, MAX_WINDOW)
 
 # Routing by default goes by measurement (tools/bench_window_attention_xl.py, profiles/NOTES_window_attention_xl.md): a shape
 # (window, map height, map width, heads) is routed here only if its fused median beat the composed median by more than the sum
@@ -46,120 +42,25 @@ def routed(window_size, Hs, Ws, num_heads):
     return shape in ACCEPTED and shape not in EXCLUDED
 
 
-def padded_tokens(window_size):
-    """NP: the window's tokens rounded up to the 32-key tile (the last axis of lse and delta)."""
-    return 32 * ((window_size * window_size + 31) // 32)
-
-
 def usable_xl_window(qkv_dtype, device, head_dim, num_heads, window_size, table, dropout_p=0.0):
     """Decides from descriptors alone (no device is touched).  `dropout_p`: the ACTIVE attention dropout probability (0 in
     eval mode)."""
-    if os.environ.get("CREAM_IRPE_FUSED", "1") == "0":
-        return False
-    if dropout_p > 0.0:
-        return False
-    if torch.device(device).type != "cuda" or qkv_dtype != torch.bfloat16:
-        return False
-    if head_dim != HEAD_DIM or not MIN_WINDOW <= window_size <= MAX_WINDOW:
-        return False
-    if not 1 <= num_heads <= MAX_HEADS:
-        return False
-    if table is None or table.dtype != torch.float32 or not table.is_contiguous():
-        return False
-    return tuple(table.shape) == ((2 * window_size - 1) ** 2, num_heads)
-
-
-def _flops(B, nW, H, N, bwd):
-    """Work the launches do on the padded key rows (recomputation included), for the timing regions.  32-deep products per
-    (i, j) and head: forward 3 (S twice, P v); backward 5 in the query launch (S and dP twice, dS k) and 4 in the key launch."""
-    NP = 32 * ((N + 31) // 32)
-    return (9 if bwd else 3) * 2.0 * B * nW * H * NP * NP * 32
-
-
-def _desc(qkv, scale, table, geometry, out, lse):
-    B, L, _, H, D = qkv.shape
-    Hs, Ws, w, shift, mask_shift = geometry
-    d = _lib.WindowAttnXlDesc()
-    _lib.set_packed_qkv(d, qkv)
-    d.out, d.lse = (out.data_ptr() if out is not None else None), lse.data_ptr()
-    d.table = table.data_ptr()
-    d.B, d.H, d.Hs, d.Ws, d.w, d.shift, d.mask_shift, d.head_dim = B, H, Hs, Ws, w, shift, mask_shift, D
-    d.scale = scale
-    return d
-
-
-def _windows(geometry):
-    Hs, Ws, w = geometry[:3]
-    return (Hs // w) * (Ws // w)
+    return _family.usable(qkv_dtype, device, head_dim, num_heads, window_size, table, dropout_p)
 
 
 def fwd_core(qkv, scale, table, geometry):
     """One forward launch: qkv (B, Hs*Ws, 3, H, 32) bf16, table ((2w-1)^2, H) fp32
     -> (out (B, Hs*Ws, H*32) bf16, lse (B*nW, H, NP) fp32 of the logits).  Outside autograd."""
-    B, L, _, H, D = qkv.shape
-    w = geometry[2]
-    out = torch.empty((B, L, H * D), dtype=qkv.dtype, device=qkv.device)
-    lse = torch.empty((B * _windows(geometry), H, padded_tokens(w)), dtype=torch.float32, device=qkv.device)
-    d = _desc(qkv, scale, table, geometry, out, lse)
-    with torch.cuda.device(qkv.device), timing.region("window_attn_xl_fwd", flops=_flops(B, _windows(geometry), H, w * w, False)):
-        rc = _lib.load().cream_window_attn_xl_fwd(ctypes.byref(d), torch.cuda.current_stream().cuda_stream)
-    _lib.check(rc, "cream_window_attn_xl_fwd")
-    return out, lse
+    return _family.fwd_core(qkv, scale, table, geometry)
 
 
 def bwd_core(dout, qkv, lse, scale, table, geometry, *, return_delta=False):
     """The two backward launches of fwd_core: -> (dqkv (B, Hs*Ws, 3, H, 32) bf16, d table).  Outside autograd.
     `return_delta`: also the (B*nW, H, NP) fp32 delta rows the query launch hands to the key launch (for the kernel tests)."""
-    B, L, _, H, D = qkv.shape
-    w = geometry[2]
-    dev = qkv.device
-    dout = dout.contiguous()
-    dqkv = torch.empty_like(qkv, memory_format=torch.contiguous_format)
-    d = _desc(qkv, scale, table, geometry, None, lse)
-    d.dout = dout.data_ptr()
-    _lib.set_packed_dqkv(d, dqkv)
-    lib = _lib.load()
-    nu = (2 * w - 1) ** 2
-    with torch.cuda.device(dev):
-        blocks = lib.cream_window_attn_xl_blocks(ctypes.byref(d))
-        if blocks < 0:
-            _lib.check(blocks, "cream_window_attn_xl_blocks")
-        psize = lib.cream_window_attn_xl_part_size(H, w)
-        if psize < 0:
-            _lib.check(psize, "cream_window_attn_xl_part_size")
-        delta = torch.empty((B * _windows(geometry), H, padded_tokens(w)), dtype=torch.float32, device=dev)
-        parts = torch.zeros((max(blocks, 1), psize), dtype=torch.float32, device=dev)
-        d.delta, d.part, d.part_blocks = delta.data_ptr(), parts.data_ptr(), max(blocks, 1)
-        with timing.region("window_attn_xl_bwd", flops=_flops(B, _windows(geometry), H, w * w, True)):
-            rc = lib.cream_window_attn_xl_bwd(ctypes.byref(d), torch.cuda.current_stream().cuda_stream)
-        _lib.check(rc, "cream_window_attn_xl_bwd")
-    dtab = parts.sum(0).reshape(nu, H)              # fixed order over the persistent grid
-    if return_delta:
-        return dqkv, dtab, delta
-    return dqkv, dtab
-
-
-class _XlWindow(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, qkv, scale, table, geometry):
-        out, lse = fwd_core(qkv, scale, table, geometry)
-        # every tensor the backward reads goes through save_for_backward (autograd's version check then sees an in-place
-        # change of a parameter between forward and backward)
-        ctx.save_for_backward(qkv, lse, table)
-        ctx.scale, ctx.geometry = scale, geometry
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        qkv, lse, table = ctx.saved_tensors
-        dqkv, dtab = bwd_core(dout, qkv, lse, ctx.scale, table, ctx.geometry)
-        return dqkv, None, dtab, None
+    return _family.bwd_core(dout, qkv, lse, scale, table, geometry, return_delta=return_delta)
 
 
 def xl_window_attention(qkv, scale, table, geometry):
     """qkv (B, Hs*Ws, 3, H, 32) bf16 -> (B, Hs*Ws, H*32).  table: the fp32 ((2w-1)^2, H) table; geometry = (Hs, Ws, w, 0, 0).
     The caller checks `usable_xl_window(...)` first; what the kernels do not implement raises."""
-    assert qkv.dim() == 5 and qkv.shape[2] == 3 and qkv.shape[4] == HEAD_DIM and qkv.stride(4) == 1
-    geometry = tuple(int(g) for g in geometry)
-    assert len(geometry) == 5 and qkv.shape[1] == geometry[0] * geometry[1]
-    return _XlWindow.apply(qkv, float(scale), table, geometry)
+    return _family.attention(qkv, scale, table, geometry)

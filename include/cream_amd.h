@@ -454,22 +454,7 @@ int cream_window_attn_large_bwd(const cream_window_attn_large_desc* d, void* str
  * CREAM_ERR_BAD_ARG before any HIP call; B == 0 is a no-op.  NP = w * w rounded up to a multiple of 32.  Nothing of size N^2
  * per window is written; no global atomics: d table comes as (part_blocks, (2w-1)^2, H) fp32 partials, every entry written
  * once, which the caller sums over the first axis. */
-typedef struct cream_window_attn_xl_desc {
-    const void *q, *k, *v;          /* bf16; element (b, n, h, :) at ptr[b*sb + n*sn + h*sh]                 */
-    int64_t sb, sn, sh;
-    void* out;                      /* (B, Hs*Ws, H, 32) bf16 (fwd only)                                   */
-    float* lse;                     /* (B * nW, H, NP): log-sum-exp of the logits (fwd: out, bwd: in)       */
-    const float* table;             /* ((2w-1)^2, H) fp32                                                  */
-    int32_t B, H, Hs, Ws, w, shift, mask_shift, head_dim;
-    float scale;
-    int32_t part_blocks;            /* bwd: cream_window_attn_xl_blocks(d), the first axis of `part`        */
-    /* backward only */
-    const void* dout;               /* (B, Hs*Ws, H, 32) bf16                                              */
-    void *dq, *dk, *dv;             /* bf16; element (b, n, h, :) at ptr[b*dsb + n*dsn + h*dsh]             */
-    int64_t dsb, dsn, dsh;
-    float* delta;                   /* (B * nW, H, NP) fp32 out: sum_j P dP of every query                 */
-    float* part;                    /* (part_blocks, cream_window_attn_xl_part_size(H, w)) fp32 out         */
-} cream_window_attn_xl_desc;
+typedef cream_window_attn_large_desc cream_window_attn_xl_desc;     /* the same fields; shift and mask_shift must be 0 */
 
 /* The argument check of the calls below alone (backward != 0: of cream_window_attn_xl_bwd, except part_blocks' value):
  * CREAM_OK or the error code.  Pure host arithmetic. */
