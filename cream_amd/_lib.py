@@ -129,6 +129,10 @@ SIGNATURES = {
     "cream_mask_grad_ws_floats": (_i64, [_i, _i]),
     "cream_mask_grad_check": (_i, [_vp, _i]),
     "cream_mask_grad_finalize": (_i, [_vp, _i, _vp]),
+    "cream_grad_finalize_compact_check": (_i, [_vp, _i]),
+    "cream_grad_finalize_compact": (_i, [_vp, _i, _vp]),
+    "cream_pad_cols": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "cream_unpad_cols": (_i, [_vp, _i, _vp, _i, _i, _i, _vp]),
     "cream_gemm_rows_per_colsum_slab": (_i, []),
     "cream_gemm_nt256": (_i, [_i]),
     "cream_gemm_nt8": (_i, [_i]),
@@ -209,6 +213,15 @@ class MaskGradJob(ctypes.Structure):
                 [(n, _i64) for n in ("ld", "pstride", "ld_w")] +
                 [(n, _c.c_int32) for n in ("nparts", "rows", "cols", "c_group", "src_bf16", "overwrite", "dr_accumulate",
                                            "dc_accumulate")])
+
+
+MAX_COMPACT_JOBS = 24
+
+
+class GradCompactJob(ctypes.Structure):
+    """struct cream_grad_compact_job of include/cream_amd.h."""
+    _fields_ = ([("dst", _vp), ("src", _vp)] + [(n, _i64) for n in ("ld_dst", "ld_src", "pstride")] +
+                [(n, _c.c_int32) for n in ("nparts", "rows", "cols", "src_bf16", "overwrite", "reserved")])
 
 
 class ImageDesc(ctypes.Structure):

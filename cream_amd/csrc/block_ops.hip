@@ -25,6 +25,7 @@
 #include "lane_ops.hpp"
 #include "cream_amd.h"
 #include "launch_ev.hpp"
+#include "grad_tree.hpp"
 
 namespace {
 using namespace cream;
@@ -462,110 +463,24 @@ __global__ __launch_bounds__(256) void colsum128_kernel(float* __restrict__ part
 }
 
 // ---- gradient finalisation: dst[map(r)][c] += sum_p part[p][r][c], many tensors per launch ---
-// One workgroup = CL consecutive 4-element chunks x PL part lanes (CL * PL = 256): part lane l
-// adds parts l, l + PL, ... in ascending order, the lanes are combined in ascending order through
-// LDS — a fixed summation tree (bit-reproducible), no atomics.
+// One workgroup = CL consecutive chunks x PL part lanes (CL * PL = 256) on the fixed summation tree of
+// grad_tree.hpp (bit-reproducible, no atomics).
 struct GradJobs {
     cream_grad_job job[CREAM_MAX_GRAD_JOBS];
     int first_block[CREAM_MAX_GRAD_JOBS + 1];
     int njobs;
 };
 
-// W = elements per chunk: 4 (fp32 partials, 16-byte loads) or 8 (bf16 partials with cols % 8 == 0: 16-byte loads too —
-// at 4 elements a bf16 load is 8 bytes per lane, which the vector memory path serves at 0.54-0.70x the 16-byte rate)
-template <int W> struct PartChunk;
-template <> struct PartChunk<4> {
-    f32x4v v;
-    __device__ __forceinline__ void zero() { v = f32x4v{0, 0, 0, 0}; }
-    __device__ __forceinline__ void add(const PartChunk& o) { v += o.v; }
-    static __device__ __forceinline__ PartChunk load(const void* src, int64_t idx, bool is_bf16) {
-        PartChunk c;
-        if (is_bf16) {
-            float f[4];
-            unpack_bf16x4(*reinterpret_cast<const u32x2v*>(reinterpret_cast<const uint16_t*>(src) + idx), f);
-            c.v = f32x4v{f[0], f[1], f[2], f[3]};
-        } else {
-            c.v = *reinterpret_cast<const f32x4v*>(reinterpret_cast<const float*>(src) + idx);
-        }
-        return c;
-    }
-    __device__ __forceinline__ void add_into(float* d) const {
-        f32x4v o = *reinterpret_cast<f32x4v*>(d);
-        o += v;
-        *reinterpret_cast<f32x4v*>(d) = o;
-    }
-    __device__ __forceinline__ void store(float* d) const { *reinterpret_cast<f32x4v*>(d) = v; }
-};
-template <> struct PartChunk<8> {                                  // bf16 sources only
-    f32x4v lo, hi;
-    __device__ __forceinline__ void zero() { lo = f32x4v{0, 0, 0, 0}; hi = lo; }
-    __device__ __forceinline__ void add(const PartChunk& o) { lo += o.lo; hi += o.hi; }
-    static __device__ __forceinline__ PartChunk load(const void* src, int64_t idx, bool) {
-        const u32x4v r = *reinterpret_cast<const u32x4v*>(reinterpret_cast<const uint16_t*>(src) + idx);
-        float a[4], b[4];
-        unpack_bf16x4(u32x2v{r[0], r[1]}, a);
-        unpack_bf16x4(u32x2v{r[2], r[3]}, b);
-        PartChunk c;
-        c.lo = f32x4v{a[0], a[1], a[2], a[3]};
-        c.hi = f32x4v{b[0], b[1], b[2], b[3]};
-        return c;
-    }
-    __device__ __forceinline__ void add_into(float* d) const {
-        f32x4v o0 = *reinterpret_cast<f32x4v*>(d), o1 = *reinterpret_cast<f32x4v*>(d + 4);
-        o0 += lo;
-        o1 += hi;
-        *reinterpret_cast<f32x4v*>(d) = o0;
-        *reinterpret_cast<f32x4v*>(d + 4) = o1;
-    }
-    __device__ __forceinline__ void store(float* d) const {
-        *reinterpret_cast<f32x4v*>(d) = lo;
-        *reinterpret_cast<f32x4v*>(d + 4) = hi;
-    }
-};
-
-// part lanes per chunk: a lane walks its parts four loads at a time, so the dependent chain of a job is nparts / (4 PL)
-// round trips — the LayerNorm jobs (1024 slab partials of a few hundred columns) set the kernel's duration at PL = 16
-// (16 round trips on 6 workgroups while the chip idles): 64 lanes there
-__host__ __device__ __forceinline__ int grad_part_lanes(int nparts) { return nparts <= 16 ? 4 : (nparts <= 64 ? 16 : 64); }
 __host__ __device__ __forceinline__ int grad_chunk_width(const cream_grad_job& b) { return b.src_bf16 && b.cols % 8 == 0 ? 8 : 4; }
 
 template <int W>
 __device__ __forceinline__ void grad_finalize_job(const cream_grad_job& jb, int block_in_job, PartChunk<W>* red) {
-    const int PL = grad_part_lanes(jb.nparts), CL = 256 / PL;
-    const int cl = threadIdx.x % CL, pl = threadIdx.x / CL;
+    const int CL = 256 / grad_part_lanes(jb.nparts);
     const int cpr = jb.cols / W;                               // chunks per row
     const int64_t nchunks = (int64_t)jb.rows * cpr;
-    const int64_t chunk = (int64_t)block_in_job * CL + cl;
-    PartChunk<W> acc;
-    acc.zero();
-    if (chunk < nchunks) {
-        const bool bf = jb.src_bf16 != 0;
-        int p = pl;
-        for (; p + 3 * PL < jb.nparts; p += 4 * PL) {          // four loads in flight
-            const PartChunk<W> a0 = PartChunk<W>::load(jb.src, (int64_t)p * jb.pstride + chunk * W, bf);
-            const PartChunk<W> a1 = PartChunk<W>::load(jb.src, (int64_t)(p + PL) * jb.pstride + chunk * W, bf);
-            const PartChunk<W> a2 = PartChunk<W>::load(jb.src, (int64_t)(p + 2 * PL) * jb.pstride + chunk * W, bf);
-            const PartChunk<W> a3 = PartChunk<W>::load(jb.src, (int64_t)(p + 3 * PL) * jb.pstride + chunk * W, bf);
-            acc.add(a0); acc.add(a1); acc.add(a2); acc.add(a3);
-        }
-        for (; p < jb.nparts; p += PL) acc.add(PartChunk<W>::load(jb.src, (int64_t)p * jb.pstride + chunk * W, bf));
-    }
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    if (PL == 64) {                                            // two levels (fixed order): 8 groups of 8 lanes, then the 8 sums
-        if (pl < 8) {
-            PartChunk<W> s = red[(8 * pl) * CL + cl];
-            for (int l = 1; l < 8; ++l) s.add(red[(8 * pl + l) * CL + cl]);
-            acc = s;
-        }
-        __syncthreads();
-        if (pl < 8) red[pl * CL + cl] = acc;
-        __syncthreads();
-    }
-    const int nl = PL == 64 ? 8 : PL;
-    if (pl == 0 && chunk < nchunks) {
-        PartChunk<W> s = red[cl];
-        for (int l = 1; l < nl; ++l) s.add(red[l * CL + cl]);
+    const int64_t chunk = (int64_t)block_in_job * CL + threadIdx.x % CL;
+    PartChunk<W> s;
+    if (grad_tree_sum<W>(s, jb.src, jb.src_bf16 != 0, jb.nparts, jb.pstride, chunk * W, chunk < nchunks, red)) {
         const int r = (int)(chunk / cpr), c = (int)(chunk - (int64_t)r * cpr) * W;
         const int rr = jb.interleave > 0 ? 3 * (r % jb.interleave) + r / jb.interleave : r;
         if (jb.overwrite) s.store(jb.dst + (int64_t)rr * jb.ld + c);      // dst = the sum (a gradient that did not exist yet: no zero fill)

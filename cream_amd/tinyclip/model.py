@@ -21,8 +21,9 @@ the encoders take `l0_module_image` / `l0_module_text` + `mask_cfg` and draw the
 does — including its asymmetry: `proj` / `text_projection` rows are multiplied by `hidden_z` (:561-565, :842-843) although
 the forward does not multiply the final LayerNorm's output, so "pruned == masked" holds for 0/1 masks only.  With every mask
 None each class runs exactly the code of the dense recipe, and the dense state-dict keys are unchanged.  The composed masked
-form (the reference's formulation, batch-first) serves fp32, CPU, QuickGELU towers, pruned towers and any call with `mha_z` /
-`ffn_z`; under bf16 autocast on the device a tower with `hidden_z` / `heads_z` / `intermediate_z` is one autograd node with
+form (the reference's formulation, batch-first) serves fp32, CPU, QuickGELU towers and any call with `mha_z` / `ffn_z`; a tower
+cut by `prune()` runs without masks, under bf16 autocast on the device as one node on zero-padded operands
+(cream_amd.tinyclip.native_pruned); under bf16 autocast on the device a tower with `hidden_z` / `heads_z` / `intermediate_z` is one autograd node with
 the masks folded into the operands (cream_amd.tinyclip.native_masked, csrc/l0_mask.hip).
 
 Not mirrored: `weight_inherit.py`'s manual inheritance, the ResNet / timm image towers, gradient checkpointing.
@@ -228,6 +229,9 @@ class Transformer(nn.Module):
                 from . import native
                 if native.supported(self, x, attn_mask, causal):   # bf16 autocast, heads of 64: the own kernels end to end
                     return native.tower(self, x, causal and attn_mask is not None)
+                from . import native_pruned
+                if native_pruned.supported(self, x, attn_mask, causal):   # a tower cut by prune(): the same node on padded operands
+                    return native_pruned.tower(self, x, causal and attn_mask is not None)
             for blk in self.resblocks:
                 x = blk(x, attn_mask)
             return x

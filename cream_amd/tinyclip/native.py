@@ -114,7 +114,7 @@ def _environment_ok(x):
 
 def _block_dense(blk, width):
     """The actual parameter shapes are those of a dense block of `width`: a tower cut down by `prune()` (a lost branch, inner
-    = 64 H_l != width, per-layer MLP widths around a smaller stream) keeps the composed path."""
+    = 64 H_l != width, per-layer MLP widths around a smaller stream) is refused here: cream_amd.tinyclip.native_pruned runs it."""
     at, mlp = blk.attn, blk.mlp
     return (tuple(at.in_proj_weight.shape) == (3 * width, width) and tuple(at.out_proj.weight.shape) == (width, width)
             and at.num_heads * 64 == width and mlp.c_fc.weight.shape[1] == width and mlp.c_proj.weight.shape[0] == width

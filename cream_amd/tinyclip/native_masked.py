@@ -18,7 +18,8 @@ library's own fixed-tree sum.  The masks enter the node as tensor inputs and the
 (after the side stream is joined), so L0Module's log-alphas get theirs through ordinary autograd of the hard-concrete sample.
 A mask that requires no gradient (eval, no_grad) costs nothing in the backward.
 
-Not here (composed path): pruned towers (inner = 64 H_l != D), mha_z / ffn_z, QuickGELU towers, fp32, CPU.
+Not here: pruned towers (inner = 64 H_l != D: cream_amd.tinyclip.native_pruned, the dense node on zero-padded operands);
+composed path: mha_z / ffn_z, QuickGELU towers, fp32, CPU.
 """
 import torch
 

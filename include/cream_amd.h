@@ -972,6 +972,39 @@ int64_t cream_mask_grad_ws_floats(int rows, int cols);
 int cream_mask_grad_check(const cream_mask_grad_job* jobs, int njobs);
 int cream_mask_grad_finalize(const cream_mask_grad_job* jobs, int njobs, void* stream);
 
+/* ---- pruned TinyCLIP towers on zero-padded operands (csrc/pruned_ops.hip) ------------------------------------------------
+ * A tower cut by prune() (TinyCLIP/src/open_clip/model.py:139-205, :317-339) has a stream of d = len(kept hidden) columns and
+ * per-layer MLP widths F_l, any integers.  It runs as the dense node on operands padded with zeros to the GEMM granularity
+ * (Dp, Fp_l: multiples of 8); parameters and gradients keep their compact shapes.
+ *
+ * Compact gradient finalisation: split-K partials laid out on the PADDED shape, added into a COMPACT fp32 gradient
+ *     dst[r * ld_dst + c] (+)= sum_p src[p * pstride + r * ld_src + c]              r < rows, c < cols
+ * rows, cols, ld_dst >= cols: any positive integers; dst 4-byte aligned only.  ld_src >= cols; src 16-byte aligned; ld_src and
+ * pstride multiples of 8 (bf16 partials) or 4 (fp32 partials).  The source is read in 16-byte chunks, so columns cols .. ld_src
+ * of a source row may be read — their values never reach dst —; nothing of dst outside rows x cols is read or written.  Per
+ * element the sum is the tree of cream_grad_finalize (csrc/grad_tree.hpp): the result equals, bit for bit, cream_grad_finalize
+ * into a (rows x ld_src) buffer followed by a slice.  Host job table, one launch; two jobs never share dst. */
+typedef struct cream_grad_compact_job {
+    float* dst;
+    const void* src;
+    int64_t ld_dst, ld_src;
+    int64_t pstride;       /* elements between consecutive parts */
+    int32_t nparts, rows, cols;
+    int32_t src_bf16;      /* partials are bf16 (1) or fp32 (0) */
+    int32_t overwrite;     /* as in cream_grad_job */
+    int32_t reserved;
+} cream_grad_compact_job;
+#define CREAM_MAX_COMPACT_JOBS 24
+int cream_grad_finalize_compact_check(const cream_grad_compact_job* jobs, int njobs);
+int cream_grad_finalize_compact(const cream_grad_compact_job* jobs, int njobs, void* stream);
+
+/* Rows between the compact and the padded layout, one launch each:
+ *     cream_pad_cols:    out (M x Dp) fp32 = in (M x d, contiguous rows, in_dtype CREAM_F32 or CREAM_BF16) in columns < d, 0 in d .. Dp
+ *     cream_unpad_cols:  out (M x d, contiguous rows, out_dtype CREAM_F32 or CREAM_BF16, round to nearest even) = in (M x Dp) fp32
+ * 1 <= d <= Dp, Dp % 4 == 0; the padded side 16-byte aligned, the compact side aligned to its element only.  M == 0: no-op. */
+int cream_pad_cols(float* out, const void* in, int in_dtype, int M, int d, int Dp, void* stream);
+int cream_unpad_cols(void* out, int out_dtype, const float* in, int M, int d, int Dp, void* stream);
+
 /* ---- the uint8 -> normalised float input transform of a batch, on the device (csrc/image_transform.hip) -----------------
  * AutoFormer/lib/datasets.py:189-220 (`build_transform`): eval = Resize(int(256 / 224 * input_size), bicubic) -> CenterCrop ->
  * ToTensor -> Normalize; train = timm's RandomResizedCropAndInterpolation(bicubic) -> RandomHorizontalFlip -> [RandAugment: host
