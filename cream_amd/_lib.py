@@ -66,6 +66,11 @@ SIGNATURES = {
     "cream_window_attn_large_blocks": (_i, [_vp]),
     "cream_window_attn_large_fwd": (_i, [_vp, _vp]),
     "cream_window_attn_large_bwd": (_i, [_vp, _vp]),
+    "cream_window_attn_mix_large_check": (_i, [_vp, _i]),
+    "cream_window_attn_mix_large_part_size": (_i, [_i, _i]),
+    "cream_window_attn_mix_large_blocks": (_i, [_vp]),
+    "cream_window_attn_mix_large_fwd": (_i, [_vp, _vp]),
+    "cream_window_attn_mix_large_bwd": (_i, [_vp, _vp]),
     "cream_window_attn_xl_check": (_i, [_vp, _i]),
     "cream_window_attn_xl_part_size": (_i, [_i, _i]),
     "cream_window_attn_xl_blocks": (_i, [_vp]),
@@ -292,6 +297,10 @@ class WindowAttnDesc(ctypes.Structure):
                 [("scale", _f), ("part_blocks", _c.c_int32)] +
                 [(n, _vp) for n in ("dout", "dq", "dk", "dv")] + [(n, _i64) for n in ("dsb", "dsn", "dsh")] +
                 [(n, _vp) for n in ("delta", "part")])
+
+
+class WindowAttnMixLargeDesc(WindowAttnDesc):
+    """struct cream_window_attn_mix_large_desc of include/cream_amd.h: the fields of the w * w <= 64 family."""
 
 
 class WindowAttnLargeDesc(ctypes.Structure):

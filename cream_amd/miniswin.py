@@ -18,8 +18,12 @@ As in the reference, a block whose map is larger than the window always has `shi
 Two paths through `SwinTransformerBlock.forward_feature`:
   * fused — under bf16 autocast on a device where `window_attn.usable_window` agrees: norm1 -> qkv on (B, L, C) ->
     `window_attn.window_attention` -> proj; no roll, no partition, no (N, N) map;
-  * composed — everything else (fp32, CPU, window 12, active attention dropout, more than 16 mixed heads): the
-    reference's arithmetic step by step.
+  * fused, window 12 (Mini-Swin-B at 384 and its plain Swin-B teacher) — the measured shapes of
+    `window_attn_mix_large.ACCEPTED` (head transforms, 9 <= w <= 12, at most 16 heads) go to
+    `window_attn_mix_large.mix_large_window_attention`, those of `PLAIN_ACCEPTED` (no head transforms, 9 <= w <= 14) to
+    `window_attn_large.large_window_attention`, the same way;
+  * composed — everything else (fp32, CPU, an unmeasured shape at window 9 and above, active attention dropout, more than 16
+    mixed heads): the reference's arithmetic step by step.
 The depthwise local convolution, patch merging and patch embedding stay with the framework.
 
 The distilling models (`SwinTransformerMiniViTDistill`, mirror of swin_transformer_minivit_distill.py:447-621, and the plain
@@ -30,7 +34,7 @@ attention's q, k, v — a `minivit_distill.QkvTap` on the fused path, the refere
 import torch
 import torch.nn as nn
 
-from . import window_attn
+from . import window_attn, window_attn_large, window_attn_mix_large
 from .minivit_distill import QkvTap
 from .rpe_attention import DropPath
 
@@ -122,11 +126,38 @@ class WindowAttention(nn.Module):
                                          self.relative_position_bias_table, proj_l, proj_w,
                                          dropout_p=self.attn_drop.p if self.training else 0.0)
 
-    def forward_map(self, qkv, geometry, proj_l=None, proj_w=None):
-        """qkv (B, Hs*Ws, 3C) of the unshifted map -> (B, Hs*Ws, C) after proj, through the fused kernels."""
+    def route(self, qkv, window_size, Hs, Ws, proj_l, proj_w):
+        """Which fused kernels take this call, from descriptors alone: 'window' (window_attn, w * w <= 64), 'mix_large'
+        (window_attn_mix_large: head transforms at 9 <= w <= 12) or 'large' (window_attn_large: no head transforms at
+        9 <= w <= 14), the last two only for the measured shapes of window_attn_mix_large.ACCEPTED / PLAIN_ACCEPTED; None:
+        the composed path."""
+        if self.usable(qkv, window_size, proj_l, proj_w):
+            return "window"
+        if self.window_size[0] != self.window_size[1] or window_size != self.window_size[0]:
+            return None
+        args = (qkv.dtype, qkv.device, self.dim // self.num_heads, self.num_heads, window_size, self.relative_position_bias_table)
+        p = self.attn_drop.p if self.training else 0.0
+        if proj_l is not None and proj_w is not None:
+            if (window_attn_mix_large.routed(window_size, Hs, Ws, self.num_heads)
+                    and window_attn_mix_large.usable_mix_large_window(*args, proj_l, proj_w, dropout_p=p)):
+                return "mix_large"
+        elif proj_l is None and proj_w is None:
+            if (window_attn_mix_large.routed_plain(window_size, Hs, Ws, self.num_heads)
+                    and window_attn_large.usable_large_window(*args, dropout_p=p)):
+                return "large"
+        return None
+
+    def forward_map(self, qkv, geometry, proj_l=None, proj_w=None, route="window"):
+        """qkv (B, Hs*Ws, 3C) of the unshifted map -> (B, Hs*Ws, C) after proj, through the fused kernels `route` names."""
         B, L, _ = qkv.shape
-        out = window_attn.window_attention(qkv.view(B, L, 3, self.num_heads, self.dim // self.num_heads), self.scale,
-                                           self.relative_position_bias_table, geometry, proj_l, proj_w)
+        qkv = qkv.view(B, L, 3, self.num_heads, self.dim // self.num_heads)
+        if route == "mix_large":
+            out = window_attn_mix_large.mix_large_window_attention(qkv, self.scale, self.relative_position_bias_table, geometry,
+                                                                   proj_l, proj_w)
+        elif route == "large":
+            out = window_attn_large.large_window_attention(qkv, self.scale, self.relative_position_bias_table, geometry)
+        else:
+            out = window_attn.window_attention(qkv, self.scale, self.relative_position_bias_table, geometry, proj_l, proj_w)
         return self.proj_drop(self.proj(out))
 
     def forward(self, x, mask=None, proj_l=None, proj_w=None):
@@ -226,10 +257,11 @@ class SwinTransformerBlock(nn.Module):
         shift = self.shift_size if is_shift else 0
         w = self.window_size
         qkv = self.attn.qkv(x)                               # per token: commutes with the roll and the partition
-        if self.attn.usable(qkv, w, proj_l, proj_w):
+        route = self.attn.route(qkv, w, H, W, proj_l, proj_w)
+        if route is not None:
             if self._taps is not None:
                 self._taps.append(QkvTap(qkv, (H, W, w, shift)))
-            x = self.attn.forward_map(qkv, (H, W, w, shift, self.shift_size), proj_l, proj_w)
+            x = self.attn.forward_map(qkv, (H, W, w, shift, self.shift_size), proj_l, proj_w, route)
         else:
             qkv = qkv.view(B, H, W, 3 * C)
             if shift > 0:
@@ -555,7 +587,8 @@ _SWIN = dict(tiny=dict(embed_dim=96, depths=[2, 2, 6, 2], num_heads=[3, 6, 12, 2
 
 def mini_swin(size='tiny', img_size=224, **kwargs):
     """Mini-Swin-{T,S,B} at 224 with window 7: every stage's blocks shared (tiny) or shared in pairs in stage 3 (small,
-    base), per-repeat LayerNorms, head transforms and local convolutions on."""
+    base), per-repeat LayerNorms, head transforms and local convolutions on.  `mini_swin('base', img_size=384,
+    window_size=12)` is the 224-to-384 fine-tuning recipe (heads 4 / 8 / 16 / 32 on maps of 96 / 48 / 24 / 12)."""
     kw = dict(img_size=img_size, patch_size=4, window_size=7, mlp_ratio=4., qkv_bias=True, is_sep_layernorm=True,
               is_transform_FFN=True, is_transform_heads=True)
     kw.update(_SWIN[size])

@@ -444,6 +444,35 @@ int cream_window_attn_large_fwd(const cream_window_attn_large_desc* d, void* str
 /* dq, dk, dv, delta and the partials of d table from dout and lse.  Two launches. */
 int cream_window_attn_large_bwd(const cream_window_attn_large_desc* d, void* stream);
 
+/* ---- fused head-mixing (shifted-)window attention for windows of 9x9 .. 12x12 (csrc/window_attn_mix_large.hip) --------
+ * The attention of Mini-Swin at window 12 (Mini-Swin-B at 384) between the qkv and proj linears: the formulas, the geometry
+ * and the layout of the partials of cream_window_attn_desc with head transforms, on key rows of 3 to 5 tiles (a two-pass
+ * softmax).  bf16 operands, fp32 accumulation; head_dim 32, square windows with 9 <= w <= 12, Hs and Ws multiples of w,
+ * shift < w, mask_shift < w; wl, bl, ww, bw all given, 1 <= H <= 16.  Anything else (32 heads included) returns
+ * CREAM_ERR_BAD_ARG before any HIP call; B == 0 is a no-op.  lse and delta are (B * nW, H, NP), NP = w * w rounded up to a
+ * multiple of 32.  Nothing of size N^2 per window is written; no global atomics: the backward's parameter gradients come as
+ * one partial per workgroup of its persistent grid, (part_blocks, part_size) fp32 = [d table ((2w-1)^2, H) | d wl (H, H) |
+ * d ww (H, H) | d bl (H) | d bw (H)], which the caller sums over the first axis. */
+typedef cream_window_attn_desc cream_window_attn_mix_large_desc;    /* the same fields; lse and delta (B * nW, H, NP) */
+
+/* The argument check of the calls below alone (backward != 0: of cream_window_attn_mix_large_bwd, except part_blocks'
+ * value): CREAM_OK or the error code.  Pure host arithmetic. */
+int cream_window_attn_mix_large_check(const cream_window_attn_mix_large_desc* d, int backward);
+
+/* Floats per workgroup partial, (2w-1)^2 H + 2 H^2 + 2 H = cream_window_attn_part_size(H, w, 1)'s formula, or
+ * CREAM_ERR_BAD_ARG.  Pure host arithmetic. */
+int cream_window_attn_mix_large_part_size(int H, int w);
+
+/* Workgroups of the backward's query launch for this descriptor's shape (B, H, Hs, Ws, w; from cream_cu_count(); the data
+ * pointers other than wl, bl, ww, bw are not looked at), 0 when B == 0, or an error code. */
+int cream_window_attn_mix_large_blocks(const cream_window_attn_mix_large_desc* d);
+
+/* out and lse from q, k, v.  One launch. */
+int cream_window_attn_mix_large_fwd(const cream_window_attn_mix_large_desc* d, void* stream);
+
+/* dq, dk, dv, delta and the partials of the parameter gradients from dout and lse.  Two launches. */
+int cream_window_attn_mix_large_bwd(const cream_window_attn_mix_large_desc* d, void* stream);
+
 /* ---- fused window attention for windows of 15x15 .. 32x32 (csrc/window_attn_xl.hip) ----------------------------------
  * The attention of a TinyViT block at high resolution (TinyViT/models/tiny_vit.py:216-286, windows of 16, 24 and 32) between
  * the qkv and proj linears, with the window partition in the addressing:
