@@ -170,6 +170,7 @@ SIGNATURES = {
     "cream_grad_clip_coef": (_i, [_vp, _vp, _i, _i, _c.c_double, _vp, _vp, _vp]),
     "cream_adamw_step_clipped": (_i, [_vp, _vp, _i, _i, _i, _c.c_double, _c.c_double, _c.c_double, _c.c_double, _i64, _vp, _vp]),
     "cream_grad_scale": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
+    "cream_adamw_step_groups": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _c.c_double, _c.c_double, _c.c_double, _i64, _vp, _vp]),
     "cream_soft_ce": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp]),
     "cream_sparse_ce": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp]),
     "cream_softmax_topk_records": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
@@ -195,6 +196,7 @@ SIGNATURES = {
 }
 
 MAX_GRAD_JOBS = 24
+ADAMW_MAX_GROUPS = 64                        # CREAM_ADAMW_MAX_GROUPS
 
 
 class GradJob(ctypes.Structure):

@@ -441,12 +441,17 @@ def param_job(p, grad=None, exp_avg=None, exp_avg_sq=None, mir=None, mir_t=None,
 
 class JobTable:
     """A device-resident table of cream_param_job + the prefix sums of their tile counts (the host
-    builds it once: the pointers of parameters, gradients, moments and copies never move)."""
+    builds it once: the pointers of parameters, gradients, moments and copies never move).  `groups`: per job the index
+    of its parameter group (an int32 device array beside the other two), for `launch` with one learning rate per group."""
 
-    def __init__(self, jobs, device):
+    def __init__(self, jobs, device, groups=None):
         import numpy as np
         lib = _lib.load()
         self.n = len(jobs)
+        self.groups = None
+        if groups is not None:
+            assert len(groups) == self.n
+            self.groups = torch.tensor(list(groups), dtype=torch.int32).to(device)
         arr = (_lib.ParamJob * self.n)(*jobs)
         first = [0]
         for j in jobs:
@@ -458,7 +463,18 @@ class JobTable:
 
     def launch(self, update=False, lr=0.0, beta1=0.9, beta2=0.999, eps=1e-8, step=1, coef=None):
         """coef: a device float (`clip_coef(...)[1:]`) every gradient value is multiplied by as it is loaded — the clipped
-        step; the gradient tensors stay as they are."""
+        step; the gradient tensors stay as they are.
+        lr: a float — one rate for every job (cream_adamw_step / cream_adamw_step_clipped) — or a sequence of per-group
+        rates for a table built with `groups` (cream_adamw_step_groups; the rates travel as kernel arguments)."""
+        if not isinstance(lr, (int, float)):
+            if self.groups is None:
+                raise ValueError("JobTable.launch: per-group learning rates need a table built with `groups`")
+            rates = (ctypes.c_double * len(lr))(*[float(r) for r in lr])
+            _lib.check(_lib.load().cream_adamw_step_groups(_p(self.jobs), _p(self.first), self.n, self.total, 1 if update else 0,
+                                                           _p(self.groups), ctypes.cast(rates, ctypes.c_void_p), len(lr),
+                                                           beta1, beta2, eps, step, _p(coef), _stream()),
+                       "cream_adamw_step_groups")
+            return
         if coef is None:
             _lib.check(_lib.load().cream_adamw_step(_p(self.jobs), _p(self.first), self.n, self.total, 1 if update else 0,
                                                     lr, beta1, beta2, eps, step, _stream()), "cream_adamw_step")

@@ -17,6 +17,7 @@ import random
 import torch
 import torch.nn.functional as F
 
+from .. import _lib
 from .. import grad_clip as _grad_clip
 from . import block as _block
 from .supernet import Vision_TransformerSuper
@@ -89,6 +90,12 @@ class NativeAdamW(torch.optim.Optimizer):
     decay from step 1 here, as they do under the reference's torch 1.7 once they were active (SURVEY 8e);
     `load_state_dict` takes max(step) and creates zero moments for parameters the file has no state for.
 
+    Parameter groups may hold different learning rates (layer-wise learning-rate decay: cream_amd.tinyvit_finetune): the
+    step then goes through cream_adamw_step_groups, which takes up to 64 rates as kernel arguments, and a changed `lr` value
+    never rebuilds the job table (a changed group MEMBERSHIP does).  With one rate in all groups the step is the launch it
+    always was.  `betas` and `eps` must be the same in every group (ValueError otherwise) and the step counter is common:
+    per-group betas / eps are not supported.
+
     Every parameter must have a `.grad` tensor when `step()` runs (the trainer zero-fills instead of
     setting None — SURVEY 8e: under the reference's torch 1.7 every tensor that was active once keeps
     receiving weight decay and moment decay); the device-resident job table is rebuilt only if a
@@ -110,7 +117,11 @@ class NativeAdamW(torch.optim.Optimizer):
                                      exp_avg_sq=torch.zeros_like(p, memory_format=torch.contiguous_format))
 
     def _build(self):
+        if len(self.param_groups) > _lib.ADAMW_MAX_GROUPS:
+            raise ValueError(f"NativeAdamW: {len(self.param_groups)} parameter groups, the kernel takes at most "
+                             f"{_lib.ADAMW_MAX_GROUPS} (CREAM_ADAMW_MAX_GROUPS)")
         wd = {p: g['weight_decay'] for g in self.param_groups for p in g['params']}
+        group_of = {p: k for k, g in enumerate(self.param_groups) for p in g['params']}
         for p in wd:                             # a torch.optim.AdamW checkpoint holds no state for never-active parameters
             st = self.state[p]
             for k in ('exp_avg', 'exp_avg_sq'):
@@ -121,7 +132,7 @@ class NativeAdamW(torch.optim.Optimizer):
         for p in wd:
             if p.grad is None:
                 p.grad = torch.zeros_like(p, memory_format=torch.contiguous_format)
-        jobs, done, self._ops = [], set(), []
+        jobs, groups, done, self._ops = [], [], set(), []     # groups[i]: the param_groups index of jobs[i]'s parameter
         for m in self.model.modules():
             if hasattr(m, 'attn') and hasattr(m, 'fc1') and hasattr(m, 'fc2'):
                 ops = _block.operands(m, fresh=False)
@@ -129,6 +140,7 @@ class NativeAdamW(torch.optim.Optimizer):
                 for p, j in ops.jobs(grads=True, states=states):
                     j.weight_decay = wd[p]
                     jobs.append(j)
+                    groups.append(group_of[p])
                     done.add(p)
         for m in self.model.modules():
             if hasattr(m, 'proj') and hasattr(m, 'patch_size') and hasattr(m, 'sample_embed_dim'):     # PatchembedSuper
@@ -138,6 +150,7 @@ class NativeAdamW(torch.optim.Optimizer):
                     if p in wd:
                         j.weight_decay = wd[p]
                         jobs.append(j)
+                        groups.append(group_of[p])
                         done.add(p)
         head = getattr(self.model, 'head', None)
         if head is not None and hasattr(head, 'sample_in_dim') and getattr(head, 'bias', None) is not None and head.weight in wd:
@@ -146,14 +159,17 @@ class NativeAdamW(torch.optim.Optimizer):
             for p, j in ops.jobs(grads=True, states=states):
                 j.weight_decay = wd[p]
                 jobs.append(j)
+                groups.append(group_of[p])
                 done.add(p)
         for p in wd:
             if p not in done:
                 jobs.append(_block.param_job(p.detach(), p.grad, states[p][0], states[p][1], weight_decay=wd[p]))
-        self._table = _block.JobTable(jobs, next(iter(wd)).device)
+                groups.append(group_of[p])
+        self._table = _block.JobTable(jobs, next(iter(wd)).device, groups=groups)
         self._plist = tuple(wd)
         self._grads = tuple(p.grad for p in wd)
         self._ptrs = self._pointer_key()
+        self._members = self._membership_key()
 
     def _pointer_key(self):
         """Raw pointers baked into the device job table: model.to(), `p.data = ...`, re-created moments or an added
@@ -161,6 +177,11 @@ class NativeAdamW(torch.optim.Optimizer):
         return tuple((p.data_ptr(), self.state[p]['exp_avg'].data_ptr(), self.state[p]['exp_avg_sq'].data_ptr())
                      if 'exp_avg' in self.state[p] else (p.data_ptr(), 0, 0)
                      for g in self.param_groups for p in g['params'])
+
+    def _membership_key(self):
+        """Which parameter sits in which group (baked into the table's job -> group array); the groups' `lr` values are not
+        part of it."""
+        return tuple(tuple(id(p) for p in g['params']) for g in self.param_groups)
 
     @torch.no_grad()
     def step(self, closure=None, max_norm=None):
@@ -170,17 +191,22 @@ class NativeAdamW(torch.optim.Optimizer):
         before clipping as a 0-dim device tensor; reading it is the caller's synchronisation."""
         assert closure is None
         if (self._table is None or any(p.grad is not g for p, g in zip(self._plist, self._grads))
-                or self._ptrs != self._pointer_key()):
+                or self._ptrs != self._pointer_key() or self._members != self._membership_key()):
             self._build()
         g0 = self.param_groups[0]
+        if any(tuple(g['betas']) != tuple(g0['betas']) or g['eps'] != g0['eps'] for g in self.param_groups):
+            raise ValueError("NativeAdamW: betas and eps must be the same in every parameter group (per-group values are not supported)")
         lr = g0['lr']
-        assert all(g['lr'] == lr for g in self.param_groups), "NativeAdamW: one learning rate for all groups"
+        if any(g['lr'] != lr for g in self.param_groups):        # one rate per group: cream_adamw_step_groups
+            lr = [float(g['lr']) for g in self.param_groups]
+        else:
+            lr = float(lr)
         coef = None
         if max_norm is not None:
             out = self._table.clip_coef(max_norm)
             self.grad_norm, coef = out[0], out[1:]
         self._steps += 1
-        self._table.launch(update=True, lr=float(lr), beta1=g0['betas'][0], beta2=g0['betas'][1], eps=g0['eps'],
+        self._table.launch(update=True, lr=lr, beta1=g0['betas'][0], beta2=g0['betas'][1], eps=g0['eps'],
                            step=self._steps, coef=coef)
         for ops in self._ops:
             ops.mark_fresh()                 # the kernel rewrote every operand copy

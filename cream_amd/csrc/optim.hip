@@ -33,7 +33,7 @@ constexpr int LP = TC + 2;                                      // LDS pitch (bf
 // columns from c of the rows r0 + 16 k + rr, k < TR / 16.
 struct TileOfBlock {
     cream_param_job jb;
-    int r0, c0, cq, rr, c;
+    int job, r0, c0, cq, rr, c;
 };
 
 __device__ __forceinline__ TileOfBlock tile_of_block(const cream_param_job* __restrict__ jobs, const int32_t* __restrict__ first_tile,
@@ -46,6 +46,7 @@ __device__ __forceinline__ TileOfBlock tile_of_block(const cream_param_job* __re
     }
     TileOfBlock w;
     w.jb = jobs[lo];
+    w.job = lo;
     const int t = (int)blockIdx.x - first_tile[lo];
     const int tcols = (w.jb.cols + TC - 1) / TC;
     w.r0 = (t / tcols) * TR;
@@ -56,17 +57,41 @@ __device__ __forceinline__ TileOfBlock tile_of_block(const cream_param_job* __re
     return w;
 }
 
+// The learning rate argument of adamw_mirror_kernel.  GROUPS false: one float, the kernel's argument list is what it always
+// was.  GROUPS true: the rates of up to CREAM_ADAMW_MAX_GROUPS parameter groups BY VALUE (256 bytes of kernel arguments: the
+// schedule changes them every step, and this way no device buffer, copy or synchronisation is involved) and the device table
+// job -> group.
+struct GroupRates {
+    const int32_t* group_of_job;
+    int ngroups;                                                // 1 .. CREAM_ADAMW_MAX_GROUPS (the launcher checks)
+    float lr[CREAM_ADAMW_MAX_GROUPS];
+};
+template <bool GROUPS> struct LrArg { using type = float; };
+template <> struct LrArg<true> { using type = GroupRates; };
+
+__device__ __forceinline__ float lr_of_job(float lr, int) { return lr; }
+// (uniform over the workgroup: a scalar load of the table entry, then of the argument; an index outside [0, ngroups) takes
+// the last group, so a bad table cannot read past the argument)
+__device__ __forceinline__ float lr_of_job(const GroupRates& r, int job)
+{
+    const int g = r.group_of_job[job];
+    return r.lr[(unsigned)g < (unsigned)r.ngroups ? g : r.ngroups - 1];
+}
+
 // CLIP: every gradient value is multiplied by *coef (one fp32 multiply, what an in-place mul_ of the gradient in front of
 // the optimizer computes) as it is loaded; the gradient in memory stays as it is.
-template <bool CLIP>
+// GROUPS: the job's learning rate is its parameter group's (LrArg); everything after that load is the same code.
+template <bool CLIP, bool GROUPS>
 __global__ __launch_bounds__(256) void adamw_mirror_kernel(const cream_param_job* __restrict__ jobs,
                                                            const int32_t* __restrict__ first_tile, int njobs, int update,
-                                                           float lr, float beta1, float beta2, float omb1, float omb2, float eps,
-                                                           float inv_bc1, float inv_sqrt_bc2, const float* __restrict__ coef)
+                                                           const typename LrArg<GROUPS>::type lr_arg, float beta1, float beta2,
+                                                           float omb1, float omb2, float eps, float inv_bc1, float inv_sqrt_bc2,
+                                                           const float* __restrict__ coef)
 {
     __shared__ uint16_t tile[TR * LP];
     const TileOfBlock w = tile_of_block(jobs, first_tile, njobs);
     const cream_param_job& jb = w.jb;
+    const float lr = lr_of_job(lr_arg, w.job);
     const int r0 = w.r0, c0 = w.c0, tid = threadIdx.x, cq = w.cq, rr = w.rr, c = w.c;
     const float cf = CLIP ? *coef : 1.f;
     const bool upd = update && jb.g != nullptr;
@@ -289,8 +314,11 @@ __global__ __launch_bounds__(256) void grad_scale_kernel(const cream_param_job* 
     }
 }
 
+// GROUPS false: `rates` is the one learning rate (fp32); true: the GroupRates of the launch.
+template <bool GROUPS>
 int launch_adamw(bool clip, const cream_param_job* jobs_dev, const int32_t* first_tile_dev, int njobs, int total_tiles, int update,
-                 double lr, double beta1, double beta2, double eps, int64_t step, const float* coef_dev, void* stream)
+                 const typename LrArg<GROUPS>::type& rates, double beta1, double beta2, double eps, int64_t step,
+                 const float* coef_dev, void* stream)
 {
     if (njobs < 0 || total_tiles < 0 || (update && step < 1) || (clip && !coef_dev)) return CREAM_ERR_BAD_ARG;
     if (njobs == 0 || total_tiles == 0) return CREAM_OK;
@@ -300,8 +328,8 @@ int launch_adamw(bool clip, const cream_param_job* jobs_dev, const int32_t* firs
         bc1 = 1.0 - pow(beta1, (double)step);
         bc2 = 1.0 - pow(beta2, (double)step);
     }
-    hipLaunchKernelGGL(clip ? adamw_mirror_kernel<true> : adamw_mirror_kernel<false>, dim3(total_tiles), dim3(256), 0,
-                       (hipStream_t)stream, jobs_dev, first_tile_dev, njobs, update, (float)lr, (float)beta1, (float)beta2,
+    const auto kernel = clip ? adamw_mirror_kernel<true, GROUPS> : adamw_mirror_kernel<false, GROUPS>;
+    hipLaunchKernelGGL(kernel, dim3(total_tiles), dim3(256), 0, (hipStream_t)stream, jobs_dev, first_tile_dev, njobs, update, rates, (float)beta1, (float)beta2,
                        (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, (float)(1.0 / bc1), (float)(1.0 / sqrt(bc2)), coef_dev);
     return hipGetLastError() == hipSuccess ? CREAM_OK : CREAM_ERR_LAUNCH;
 }
@@ -319,13 +347,29 @@ int cream_param_job_tiles(int rows, int cols)
 int cream_adamw_step(const cream_param_job* jobs_dev, const int32_t* first_tile_dev, int njobs, int total_tiles, int update,
                      double lr, double beta1, double beta2, double eps, int64_t step, void* stream)
 {
-    return launch_adamw(false, jobs_dev, first_tile_dev, njobs, total_tiles, update, lr, beta1, beta2, eps, step, nullptr, stream);
+    return launch_adamw<false>(false, jobs_dev, first_tile_dev, njobs, total_tiles, update, (float)lr, beta1, beta2, eps, step, nullptr,
+                               stream);
 }
 
 int cream_adamw_step_clipped(const cream_param_job* jobs_dev, const int32_t* first_tile_dev, int njobs, int total_tiles, int update,
                              double lr, double beta1, double beta2, double eps, int64_t step, const float* coef_dev, void* stream)
 {
-    return launch_adamw(true, jobs_dev, first_tile_dev, njobs, total_tiles, update, lr, beta1, beta2, eps, step, coef_dev, stream);
+    return launch_adamw<false>(true, jobs_dev, first_tile_dev, njobs, total_tiles, update, (float)lr, beta1, beta2, eps, step, coef_dev,
+                               stream);
+}
+
+int cream_adamw_step_groups(const cream_param_job* jobs_dev, const int32_t* first_tile_dev, int njobs, int total_tiles, int update,
+                            const int32_t* group_of_job_dev, const double* lr_of_group, int ngroups, double beta1, double beta2,
+                            double eps, int64_t step, const float* coef_dev, void* stream)
+{
+    if (ngroups < 1 || ngroups > CREAM_ADAMW_MAX_GROUPS || !lr_of_group) return CREAM_ERR_BAD_ARG;
+    if (njobs > 0 && !group_of_job_dev) return CREAM_ERR_BAD_ARG;
+    GroupRates rates;
+    rates.group_of_job = group_of_job_dev;
+    rates.ngroups = ngroups;
+    for (int k = 0; k < CREAM_ADAMW_MAX_GROUPS; ++k) rates.lr[k] = k < ngroups ? (float)lr_of_group[k] : 0.f;
+    return launch_adamw<true>(coef_dev != nullptr, jobs_dev, first_tile_dev, njobs, total_tiles, update, rates, beta1, beta2, eps, step,
+                              coef_dev, stream);
 }
 
 int cream_grad_clip_coef(const cream_param_job* jobs_dev, const int32_t* first_tile_dev, int njobs, int total_tiles,

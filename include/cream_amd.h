@@ -909,6 +909,26 @@ int cream_adamw_step_clipped(const cream_param_job* jobs_dev, const int32_t* fir
 int cream_grad_scale(const cream_param_job* jobs_dev, const int32_t* first_tile_dev, int njobs, int total_tiles,
                      const float* coef_dev, void* stream);
 
+/* cream_adamw_step with one learning rate PER PARAMETER GROUP — the layer-wise learning-rate decay of TinyViT's fine-tune
+ * recipes (TinyViT/optimizer.py:13-37 with tinyvit_utils.divide_param_groups_by_lr_scale: one torch.optim.AdamW group per
+ * lr_scale and weight-decay class, whose `lr` LRSchedulerWrapper rewrites after every scheduler call).
+ *     group_of_job_dev   njobs int32 in DEVICE memory: the group of every job of the table
+ *     lr_of_group        ngroups doubles in HOST memory, 1 <= ngroups <= CREAM_ADAMW_MAX_GROUPS; rounded to fp32 and passed
+ *                        to the kernel by value (256 bytes of kernel arguments), so a schedule that changes them every step
+ *                        costs no device buffer, no copy and no synchronisation
+ * A job's workgroups take lr_of_group[group_of_job_dev[job]]; a stored index outside [0, ngroups) is CLAMPED to the last
+ * group (never read past the argument).  Everything else is cream_adamw_step's: the per-element arithmetic of a job is the
+ * instruction sequence of the ungrouped kernel run with that job's rate, weight_decay stays per job, the copies, g == NULL
+ * and update == 0 behave alike.  beta1, beta2, eps and the step counter (bias correction) stay COMMON to all groups.
+ * coef_dev NULL: unclipped; else cream_adamw_step_clipped's coefficient (cream_grad_clip_coef's norm is global over all
+ * groups, as clip_grad_norm_ over model.parameters() is).
+ * CREAM_ERR_BAD_ARG without launching: ngroups outside 1..CREAM_ADAMW_MAX_GROUPS, a NULL lr_of_group, a NULL
+ * group_of_job_dev with njobs > 0, update with step < 1, NULL tables; njobs == 0 or total_tiles == 0 is a no-op. */
+#define CREAM_ADAMW_MAX_GROUPS 64
+int cream_adamw_step_groups(const cream_param_job* jobs_dev, const int32_t* first_tile_dev, int njobs, int total_tiles,
+                            int update, const int32_t* group_of_job_dev, const double* lr_of_group, int ngroups,
+                            double beta1, double beta2, double eps, int64_t step, const float* coef_dev, void* stream);
+
 /* Gradient finalisation for the weight-entangled parameters: every tensor of a block gets
  *     dst[map(r)*ld + c] += sum_p src[p*pstride + r*cols + c]          r < rows, c < cols
  * in ONE launch — dst is the ACTIVE SLICE W[:out, :in] of the fp32 super-weight gradient
