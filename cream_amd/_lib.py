@@ -80,6 +80,10 @@ SIGNATURES = {
     "cream_token_dwconv3_blocks": (_i, [_vp]),
     "cream_token_dwconv3_fwd": (_i, [_vp, _vp]),
     "cream_token_dwconv3_bwd": (_i, [_vp, _vp]),
+    "cream_token_dwconv7_part_size": (_i, [_i]),
+    "cream_token_dwconv7_blocks": (_i, [_vp]),
+    "cream_token_dwconv7_fwd": (_i, [_vp, _vp]),
+    "cream_token_dwconv7_bwd": (_i, [_vp, _vp]),
     "cream_cga_attn_check": (_i, [_vp]),
     "cream_cga_attn_fwd": (_i, [_vp, _vp]),
     "cream_relation_loss_check": (_i, [_vp]),
@@ -323,6 +327,13 @@ class TokenDwconv3Desc(ctypes.Structure):
     """struct cream_token_dwconv3_desc of include/cream_amd.h."""
     _fields_ = ([(n, _vp) for n in ("x", "w", "bias", "y")] +
                 [(n, _c.c_int32) for n in ("B", "Hs", "Ws", "C", "dtype", "part_blocks")] +
+                [(n, _vp) for n in ("dy", "dx", "part")])
+
+
+class TokenDwconv7Desc(ctypes.Structure):
+    """struct cream_token_dwconv7_desc of include/cream_amd.h."""
+    _fields_ = ([(n, _vp) for n in ("x", "w", "bias", "y")] +
+                [(n, _c.c_int32) for n in ("B", "Hs", "Ws", "C", "dtype", "part_blocks", "residual")] +
                 [(n, _vp) for n in ("dy", "dx", "part")])
 
 

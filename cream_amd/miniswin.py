@@ -24,7 +24,16 @@ Two paths through `SwinTransformerBlock.forward_feature`:
     `window_attn_large.large_window_attention`, the same way;
   * composed — everything else (fp32, CPU, an unmeasured shape at window 9 and above, active attention dropout, more than 16
     mixed heads): the reference's arithmetic step by step.
-The depthwise local convolution, patch merging and patch embedding stay with the framework.
+The local convolution (`SwinTransformerBlock.local_convolution`): LayerNorm, then `x + conv(x)` —
+  * fused — on a device, with or without autocast, when `fused_local_conv` is set and `token_conv.usable_token_conv7` holds
+    for the repeat's `nn.Conv2d`: the LayerNorm's output goes to `token_conv.token_dwconv7(..., residual=True)` on the token
+    layout in its own dtype.  Under bf16 autocast that is fp32 (LayerNorm's output and the residual stream are fp32 there), so
+    the branch spends no bf16 rounding — deliberately unlike the framework's autocast convolution, which rounds input, taps
+    and output to bf16.  Every shape of the published recipes measured faster fused than composed
+    (profiles/NOTES_miniswin_local_conv.md), so no shape is excluded on speed grounds;
+  * composed — CPU tensors, `fused_local_conv=False`, a convolution someone replaced, fp16: the reference's transposes to NCHW
+    and back around `nn.Conv2d`.
+`CREAM_IRPE_FUSED` switches the attention only.  Patch merging and patch embedding stay with the framework.
 
 The distilling models (`SwinTransformerMiniViTDistill`, mirror of swin_transformer_minivit_distill.py:447-621, and the plain
 Swin teacher `SwinTransformerDistill`, mirror of swin_transformer_distill.py) return, per layer id listed, a TAP of the
@@ -34,7 +43,7 @@ attention's q, k, v — a `minivit_distill.QkvTap` on the fused path, the refere
 import torch
 import torch.nn as nn
 
-from . import window_attn, window_attn_large, window_attn_mix_large
+from . import token_conv, window_attn, window_attn_large, window_attn_mix_large
 from .minivit_distill import QkvTap
 from .rpe_attention import DropPath
 
@@ -189,16 +198,18 @@ class WindowAttention(nn.Module):
 
 
 class SwinTransformerBlock(nn.Module):
-    """:166-396."""
+    """:166-396.  `fused_local_conv`: route the depthwise 7 x 7 convolution to cream_amd.token_conv where it is covered."""
 
     def __init__(self, dim, input_resolution, num_heads, window_size=7, mlp_ratio=4., qkv_bias=True, qk_scale=None, drop=0.,
                  attn_drop=0., shift_size=0., drop_path=(0,), act_layer=nn.GELU, norm_layer=nn.LayerNorm,
-                 is_init_window_shift=False, is_sep_layernorm=False, is_transform_FFN=False, is_transform_heads=False):
+                 is_init_window_shift=False, is_sep_layernorm=False, is_transform_FFN=False, is_transform_heads=False,
+                 fused_local_conv=True):
         super().__init__()
         self.dim = dim
         self.input_resolution = input_resolution
         self.num_heads = num_heads
         self.window_size = window_size
+        self.fused_local_conv = fused_local_conv
         self.mlp_ratio = mlp_ratio
         self.share_num = len(drop_path)
         self.is_init_window_shift = is_init_window_shift
@@ -276,12 +287,33 @@ class SwinTransformerBlock(nn.Module):
             x = x.reshape(B, H * W, C)
         x = shortcut + self.drop_path[layer_index](x)
         if self.local_conv_list is not None:
-            x = self.local_norm_list[layer_index](x)
-            x = x.permute(0, 2, 1).reshape(B, C, H, W)
-            x = x + self.local_conv_list[layer_index](x)
-            x = x.reshape(B, C, H * W).permute(0, 2, 1)
+            x = self.local_convolution(x, layer_index)
         norm2 = self.norm2_list[layer_index] if self.is_sep_layernorm else self.norm2
         return x + self.drop_path[layer_index](self.mlp(norm2(x)))
+
+    def local_conv_is_fused(self, dtype, device, layer_index=0):
+        """Whether repeat `layer_index`'s convolution goes to the token-layout kernels for an input of this dtype on this
+        device, from descriptors alone."""
+        c = self.local_conv_list[layer_index]
+        return bool(self.fused_local_conv and type(c) is nn.Conv2d and c.padding_mode == 'zeros'
+                    and c.in_channels == c.out_channels == self.dim and c.weight.dtype == torch.float32
+                    and token_conv.usable_token_conv7(dtype, device, self.dim, c.kernel_size, c.stride, c.padding, c.dilation,
+                                                      c.groups))
+
+    def local_convolution(self, x, layer_index):
+        """:328-332: x (B, H*W, C) -> y + conv(y) with y = local_norm(x), repeat `layer_index`'s LayerNorm and depthwise 7 x 7
+        convolution.  The fused branch hands the LayerNorm's output to the token-layout kernel in its own dtype — fp32 under
+        bf16 autocast, so it spends no bf16 rounding where the framework's autocast convolution rounds input, taps and output
+        to bf16; the composed branch is the reference's lines."""
+        H, W = self.input_resolution
+        B, L, C = x.shape
+        x = self.local_norm_list[layer_index](x)
+        if self.local_conv_is_fused(x.dtype, x.device, layer_index):
+            c = self.local_conv_list[layer_index]
+            return token_conv.token_dwconv7(x, c.weight, c.bias, (H, W), residual=True)
+        x = x.permute(0, 2, 1).reshape(B, C, H, W)
+        x = x + self.local_conv_list[layer_index](x)
+        return x.reshape(B, C, H * W).permute(0, 2, 1)
 
     def forward(self, x):
         shift = self.is_init_window_shift
@@ -344,7 +376,8 @@ class BasicLayer(nn.Module):
 
     def __init__(self, dim, input_resolution, depth, num_heads, window_size, mlp_ratio=4., qkv_bias=True, qk_scale=None, drop=0.,
                  attn_drop=0., drop_path=(0.,), norm_layer=nn.LayerNorm, downsample=None, use_checkpoint=False,
-                 is_sep_layernorm=False, is_transform_FFN=False, is_transform_heads=False, separate_layer_num=1):
+                 is_sep_layernorm=False, is_transform_FFN=False, is_transform_heads=False, separate_layer_num=1,
+                 fused_local_conv=True):
         super().__init__()
         assert isinstance(drop_path, list)
         self.dim = dim
@@ -360,7 +393,7 @@ class BasicLayer(nn.Module):
                                  drop_path=drop_path[i * self.share_times:min((i + 1) * self.share_times, depth)],
                                  norm_layer=norm_layer, is_init_window_shift=(i * self.share_times) % 2 == 1,
                                  is_sep_layernorm=is_sep_layernorm, is_transform_FFN=is_transform_FFN,
-                                 is_transform_heads=is_transform_heads)
+                                 is_transform_heads=is_transform_heads, fused_local_conv=fused_local_conv)
             for i in range(separate_layer_num)])
         self.downsample = downsample(input_resolution, dim=dim, norm_layer=norm_layer) if downsample is not None else None
 
@@ -405,7 +438,8 @@ class SwinBasicLayer(BasicLayer):
                                  shift_size=0 if i % 2 == 0 else window_size // 2, mlp_ratio=mlp_ratio, qkv_bias=qkv_bias,
                                  qk_scale=qk_scale, drop=drop, attn_drop=attn_drop,
                                  drop_path=[drop_path[i] if isinstance(drop_path, (list, tuple)) else drop_path],
-                                 norm_layer=norm_layer, is_init_window_shift=i % 2 == 1)
+                                 norm_layer=norm_layer, is_init_window_shift=i % 2 == 1,
+                                 fused_local_conv=minivit.get("fused_local_conv", True))
             for i in range(depth)])
         self.downsample = downsample(input_resolution, dim=dim, norm_layer=norm_layer) if downsample is not None else None
 
@@ -439,7 +473,7 @@ class SwinTransformerMiniViT(nn.Module):
                  num_heads=(3, 6, 12, 24), window_size=7, mlp_ratio=4., qkv_bias=True, qk_scale=None, drop_rate=0.,
                  attn_drop_rate=0., drop_path_rate=0.1, norm_layer=nn.LayerNorm, ape=False, patch_norm=True, use_checkpoint=False,
                  is_sep_layernorm=False, is_transform_FFN=False, is_transform_heads=False, separate_layer_num_list=(1, 1, 2, 1),
-                 **kwargs):
+                 fused_local_conv=True, **kwargs):
         super().__init__()
         self.num_classes = num_classes
         self.num_layers = len(depths)
@@ -468,7 +502,7 @@ class SwinTransformerMiniViT(nn.Module):
                 drop=drop_rate, attn_drop=attn_drop_rate, drop_path=dpr[sum(depths[:i]):sum(depths[:i + 1])], norm_layer=norm_layer,
                 downsample=PatchMerging if i < self.num_layers - 1 else None, use_checkpoint=use_checkpoint,
                 is_sep_layernorm=is_sep_layernorm, is_transform_FFN=is_transform_FFN, is_transform_heads=is_transform_heads,
-                separate_layer_num=separate_layer_num_list[i]))
+                separate_layer_num=separate_layer_num_list[i], fused_local_conv=fused_local_conv))
         self.norm = norm_layer(self.num_features)
         self.avgpool = nn.AdaptiveAvgPool1d(1)
         self.head = nn.Linear(self.num_features, num_classes) if num_classes > 0 else nn.Identity()
@@ -476,6 +510,18 @@ class SwinTransformerMiniViT(nn.Module):
         for m in self.modules():
             if isinstance(m, SwinTransformerBlock):
                 m.custom_init_weights()
+
+    @property
+    def fused_local_conv(self):
+        """Whether every block routes its local convolution to cream_amd.token_conv where it is covered (a plain attribute of
+        the blocks: no parameter, no buffer)."""
+        return all(b.fused_local_conv for layer in self.layers for b in layer.blocks)
+
+    @fused_local_conv.setter
+    def fused_local_conv(self, flag):
+        for layer in self.layers:
+            for b in layer.blocks:
+                b.fused_local_conv = bool(flag)
 
     @staticmethod
     def _init_weights(m):
@@ -565,12 +611,13 @@ class SwinTransformerDistill(SwinTransformerMiniViTDistill):
     def __init__(self, img_size=224, patch_size=4, in_chans=3, num_classes=1000, embed_dim=96, depths=(2, 2, 6, 2),
                  num_heads=(3, 6, 12, 24), window_size=7, mlp_ratio=4., qkv_bias=True, qk_scale=None, drop_rate=0.,
                  attn_drop_rate=0., drop_path_rate=0.1, norm_layer=nn.LayerNorm, ape=False, patch_norm=True, use_checkpoint=False,
-                 is_student=False, fit_size_C=128, **kwargs):
+                 is_student=False, fit_size_C=128, fused_local_conv=True, **kwargs):
         super().__init__(img_size=img_size, patch_size=patch_size, in_chans=in_chans, num_classes=num_classes, embed_dim=embed_dim,
                          depths=depths, num_heads=num_heads, window_size=window_size, mlp_ratio=mlp_ratio, qkv_bias=qkv_bias,
                          qk_scale=qk_scale, drop_rate=drop_rate, attn_drop_rate=attn_drop_rate, drop_path_rate=drop_path_rate,
                          norm_layer=norm_layer, ape=ape, patch_norm=patch_norm, use_checkpoint=use_checkpoint,
-                         separate_layer_num_list=list(depths), is_student=is_student, fit_size_C=fit_size_C)
+                         separate_layer_num_list=list(depths), is_student=is_student, fit_size_C=fit_size_C,
+                         fused_local_conv=fused_local_conv)
 
     def forward(self, x, layer_id_list=(), is_attn_loss=False, is_hidden_loss=False, is_hidden_org=False):
         return super().forward(x, layer_id_list, is_attn_loss, is_hidden_loss, is_hidden_org)
@@ -588,7 +635,8 @@ _SWIN = dict(tiny=dict(embed_dim=96, depths=[2, 2, 6, 2], num_heads=[3, 6, 12, 2
 def mini_swin(size='tiny', img_size=224, **kwargs):
     """Mini-Swin-{T,S,B} at 224 with window 7: every stage's blocks shared (tiny) or shared in pairs in stage 3 (small,
     base), per-repeat LayerNorms, head transforms and local convolutions on.  `mini_swin('base', img_size=384,
-    window_size=12)` is the 224-to-384 fine-tuning recipe (heads 4 / 8 / 16 / 32 on maps of 96 / 48 / 24 / 12)."""
+    window_size=12)` is the 224-to-384 fine-tuning recipe (heads 4 / 8 / 16 / 32 on maps of 96 / 48 / 24 / 12).
+    `fused_local_conv=False` keeps the local convolutions on the framework's path."""
     kw = dict(img_size=img_size, patch_size=4, window_size=7, mlp_ratio=4., qkv_bias=True, is_sep_layernorm=True,
               is_transform_FFN=True, is_transform_heads=True)
     kw.update(_SWIN[size])

@@ -539,6 +539,44 @@ int cream_token_dwconv3_fwd(const cream_token_dwconv3_desc* d, void* stream);
 /* dx and the partials of dw and dbias from dy and x.  Two launches. */
 int cream_token_dwconv3_bwd(const cream_token_dwconv3_desc* d, void* stream);
 
+/* ---- depthwise 7 x 7 convolution on the token layout, residual fused (csrc/token_dwconv7.hip) ------------------------
+ * The local convolution of a Mini-Swin block repeat (MiniViT/Mini-Swin/models/swin_transformer_minivit.py:328-332) without
+ * the transposes to NCHW and back: x (B, Hs*Ws, C) contiguous, token n = i * Ws + j; stride 1, zero padding 3, r = residual:
+ *     y[b, i, j, c]  = bias[c] + sum_{di, dj} w[c, di, dj] x[b, i + di - 3, j + dj - 3, c]   (+ x[b, i, j, c] if r)
+ *     dx[b, i, j, c] = sum_{di, dj} w[c, di, dj] dy[b, i - di + 3, j - dj + 3, c]            (+ dy[b, i, j, c] if r)
+ *     dw[c, di, dj]  = sum_{b, i, j} dy[b, i, j, c] x[b, i + di - 3, j + dj - 3, c],   dbias[c] = sum_{b, i, j} dy[b, i, j, c]
+ * x, y, dy, dx in `dtype` (CREAM_BF16 or CREAM_F32), taps, bias and the partials fp32; fp32 accumulation, bias first, then
+ * the taps in row-major order of the input offset, then the residual.  C a multiple of 8, B, Hs, Ws >= 1, residual 0 or 1,
+ * every base 16-byte aligned (bias: 4); anything else returns CREAM_ERR_BAD_ARG (CREAM_ERR_BAD_DTYPE) before any HIP call.
+ * No atomics: dw and dbias come as (part_blocks, cream_token_dwconv7_part_size(C)) fp32 partials [dw (C, 49) | dbias (C)],
+ * every entry written once, which the caller sums over the first axis. */
+typedef struct cream_token_dwconv7_desc {
+    const void* x;                  /* (B, Hs*Ws, C)                                                        */
+    const float* w;                 /* (C, 1, 7, 7) fp32 contiguous                                         */
+    const float* bias;              /* (C) fp32 or NULL (fwd only)                                          */
+    void* y;                        /* (B, Hs*Ws, C) (fwd only)                                             */
+    int32_t B, Hs, Ws, C, dtype;
+    int32_t part_blocks;            /* bwd: cream_token_dwconv7_blocks(d), the first axis of `part`         */
+    int32_t residual;               /* 1: y += x, dx += dy                                                  */
+    /* backward only */
+    const void* dy;                 /* (B, Hs*Ws, C)                                                        */
+    void* dx;                       /* (B, Hs*Ws, C)                                                        */
+    float* part;                    /* (part_blocks, 50 C) fp32 out                                         */
+} cream_token_dwconv7_desc;
+
+/* Floats per partial, 50 C, or CREAM_ERR_BAD_ARG.  Pure host arithmetic. */
+int cream_token_dwconv7_part_size(int C);
+
+/* Workgroups along the tile axis of every launch for this descriptor's shape (B, Hs, Ws, C, dtype; from cream_cu_count();
+ * the data pointers are not looked at), or an error code. */
+int cream_token_dwconv7_blocks(const cream_token_dwconv7_desc* d);
+
+/* y from x, w and bias.  One launch. */
+int cream_token_dwconv7_fwd(const cream_token_dwconv7_desc* d, void* stream);
+
+/* dx and the partials of dw and dbias from dy and x.  Two launches. */
+int cream_token_dwconv7_bwd(const cream_token_dwconv7_desc* d, void* stream);
+
 /* ---- EfficientViT's cascaded group attention, inference (csrc/cga_attn.hip) ------------------------------------------
  * What CascadedGroupAttention.forward (EfficientViT/classification/model/efficientvit.py:159-180) computes between its input
  * and the ReLU in front of `proj`, BatchNorm folded, for every w x w window of the map in one launch.  With Cg = C / h and
