@@ -16,6 +16,9 @@ _ERRORS = {
     -2: "CREAM_ERR_BAD_DTYPE (element type not supported by this entry point)",
     -3: "CREAM_ERR_LAUNCH (HIP kernel launch failed)",
     -4: "CREAM_ERR_TOO_LARGE (shape exceeds what the kernel family supports)",
+    -5: "CREAM_ERR_CHANNEL_STRIDE (the channel stride of a (B, H, W, C) view is not 1)",
+    -6: "CREAM_ERR_BAD_STRIDE (a stride is negative, not a multiple of 8, or tokens overlap)",
+    -7: "CREAM_ERR_BAD_SHAPE (a channel count or a map size outside the covered range)",
 }
 
 # dtype enum of include/cream_amd.h
@@ -86,6 +89,10 @@ SIGNATURES = {
     "cream_token_dwconv7_bwd": (_i, [_vp, _vp]),
     "cream_cga_attn_check": (_i, [_vp]),
     "cream_cga_attn_fwd": (_i, [_vp, _vp]),
+    "cream_evit_dwffn_check": (_i, [_vp]),
+    "cream_evit_dwffn_fwd": (_i, [_vp, _vp]),
+    "cream_evit_pw_residual_check": (_i, [_vp]),
+    "cream_evit_pw_residual_fwd": (_i, [_vp, _vp]),
     "cream_relation_loss_check": (_i, [_vp]),
     "cream_relation_loss_blocks": (_i, [_vp]),
     "cream_relation_loss": (_i, [_vp, _vp]),
@@ -342,6 +349,21 @@ class CgaDesc(ctypes.Structure):
     _fields_ = ([("x", _vp)] + [(n, _i64) for n in ("xsb", "xsy", "xsx")] +
                 [(n, _vp) for n in ("wqkv", "bqkv", "dw", "dwb", "ab", "out")] +
                 [(n, _c.c_int32) for n in ("B", "Hs", "Ws", "w", "h", "Cg", "relu")] + [("ks", _c.c_int32 * 4), ("scale", _f)])
+
+
+class EvitDwffnDesc(ctypes.Structure):
+    """struct cream_evit_dwffn_desc of include/cream_amd.h."""
+    _fields_ = ([("x", _vp)] + [(n, _i64) for n in ("xsb", "xsy", "xsx", "xsc")] +
+                [(n, _vp) for n in ("taps", "dwb", "w1", "b1", "w2", "b2", "out")] +
+                [(n, _c.c_int32) for n in ("B", "H", "W", "C", "Ch")])
+
+
+class EvitPwDesc(ctypes.Structure):
+    """struct cream_evit_pw_desc of include/cream_amd.h."""
+    _fields_ = ([("a", _vp)] + [(n, _i64) for n in ("asb", "asy", "asx", "asc")] +
+                [("res", _vp)] + [(n, _i64) for n in ("rsb", "rsy", "rsx", "rsc")] +
+                [(n, _vp) for n in ("w", "b", "out")] +
+                [(n, _c.c_int32) for n in ("B", "H", "W", "Cin", "Cout")])
 
 
 class RelationSide(ctypes.Structure):

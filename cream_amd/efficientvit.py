@@ -23,7 +23,15 @@ Two paths through `LocalWindowAttention.forward`:
   * composed — everything else (training mode, fp32, the CPU, padded maps, out-of-range shapes): the reference's arithmetic
     step by step, with autograd through plain modules.  Training is out of scope for the kernel: a BatchNorm sits between every
     head's projection and its attention and needs batch statistics over all windows.
-The convolutions, BatchNorm, the FFNs and the classifier stay with the framework.
+
+Two paths through `EfficientViT.forward`:
+  * tokens — `fused_blocks` set, `CREAM_IRPE_FUSED` not 0, eval mode, a device tensor under bf16 autocast, nothing requiring a
+    gradient: `patch_embed`'s output is brought to (B, H, W, C) bf16 once and stays there up to the pooling.  Every depthwise
+    3 x 3 + FFN pair (two per block, one on either side of a `PatchMerging`) is ONE launch of cream_amd.evit_ffn, the mixer is
+    the cascaded group attention launch followed by `proj` + residual in one launch; `PatchMerging` runs with the framework on
+    the channels-last view of the token tensor.  A pair or a mixer the kernels do not cover runs composed on the view.
+  * composed — everything else: the modules one after the other on NCHW, as the reference does.
+The stem, `PatchMerging`, BatchNorm in training mode and the classifier stay with the framework.
 """
 import itertools
 import os
@@ -32,7 +40,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import cga_attn
+from . import cga_attn, evit_ffn
 
 
 def _trunc_normal(t, std=.02):
@@ -289,6 +297,28 @@ class LocalWindowAttention(nn.Module):
         return x.permute(0, 3, 1, 2)
 
 
+def _kernel_view(t):
+    """(B, H, W, C) -> the same values as a tensor the token kernels take: itself where its dtype, strides and base allow."""
+    return t if evit_ffn.view_ok(t) else t.to(torch.bfloat16).contiguous()
+
+
+def _conv_of(m):
+    return m if isinstance(m, nn.Conv2d) else m.c
+
+
+def dw_ffn_tokens(dw, ffn, t):
+    """The pair of `Residual`s dw (depthwise 3 x 3) and ffn on t (B, H, W, C): one launch where `evit_ffn.usable_dwffn` holds,
+    the two modules on the NCHW view otherwise."""
+    c1 = _conv_of(ffn.m.pw1)
+    if evit_ffn.usable_dwffn(torch.bfloat16, t.device, c1.in_channels, c1.out_channels, t.shape[1], t.shape[2]):
+        return evit_ffn.fwd_dwffn(_kernel_view(t), evit_ffn.fold_dwffn(dw, ffn))
+    return ffn(dw(t.permute(0, 3, 1, 2))).permute(0, 2, 3, 1)
+
+
+def _is_dw_ffn(m):
+    return isinstance(m, nn.Sequential) and len(m) == 2 and all(isinstance(r, Residual) for r in m) and isinstance(m[1].m, FFN)
+
+
 class EfficientViTBlock(nn.Module):
     """:250-282."""
 
@@ -306,6 +336,23 @@ class EfficientViTBlock(nn.Module):
     def forward(self, x):
         return self.ffn1(self.dw1(self.mixer(self.ffn0(self.dw0(x)))))
 
+    def forward_tokens(self, t):
+        """t (B, H, W, C) bf16 -> (B, H, W, C) bf16: four launches where everything is covered (eval mode, no gradients)."""
+        t = dw_ffn_tokens(self.dw0, self.ffn0, t)
+        m = self.mixer.m
+        v = t.permute(0, 3, 1, 2)                   # the NCHW view of the token tensor
+        if m.is_fused(v):
+            a = m.attn
+            o = cga_attn.fwd_core(_kernel_view(t), cga_attn.fold(a), min(m.window_resolution, m.resolution), a.scale)
+            proj = _conv_of(a.proj[1])
+            if evit_ffn.usable_pw(torch.bfloat16, t.device, proj.in_channels, proj.out_channels):
+                t = evit_ffn.fwd_pw_residual(o, _kernel_view(t), evit_ffn.fold_pw(a.proj[1]))
+            else:
+                t = t + a.proj[1](o.permute(0, 3, 1, 2)).permute(0, 2, 3, 1)
+        else:
+            t = t + m(v).permute(0, 2, 3, 1)
+        return dw_ffn_tokens(self.dw1, self.ffn1, t)
+
 
 def _dw_ffn(ed, resolution):
     return nn.Sequential(Residual(Conv2d_BN(ed, ed, 3, 1, 1, groups=ed, resolution=resolution)),
@@ -317,8 +364,9 @@ class EfficientViT(nn.Module):
 
     def __init__(self, img_size=224, patch_size=16, in_chans=3, num_classes=1000, stages=['s', 's', 's'], embed_dim=[64, 128, 192],
                  key_dim=[16, 16, 16], depth=[1, 2, 3], num_heads=[4, 4, 4], window_size=[7, 7, 7], kernels=[5, 5, 5, 5],
-                 down_ops=[['subsample', 2], ['subsample', 2], ['']], distillation=False, fused_attention=True):
+                 down_ops=[['subsample', 2], ['subsample', 2], ['']], distillation=False, fused_attention=True, fused_blocks=True):
         super().__init__()
+        self.fused_blocks = bool(fused_blocks)
         resolution = img_size
         e0 = embed_dim[0]
         self.patch_embed = nn.Sequential(
@@ -364,9 +412,32 @@ class EfficientViT(nn.Module):
     def no_weight_decay(self):
         return {k for k in self.state_dict().keys() if 'attention_biases' in k}
 
+    def is_tokens(self, x):
+        """The path decision for this input: from the model's state and the tensor's descriptors alone (the rule of
+        `LocalWindowAttention.is_fused`)."""
+        if not self.fused_blocks or self.training or os.environ.get("CREAM_IRPE_FUSED", "1") == "0" or not _bf16_autocast(x):
+            return False
+        return not (torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())))
+
+    def forward_tokens(self, x):
+        """x (B, 3, H, W) -> the pooled features (B, C): the map stays (B, H, W, C) bf16 from the stem to the pooling."""
+        t = _kernel_view(self.patch_embed(x).permute(0, 2, 3, 1))
+        for stage in (self.blocks1, self.blocks2, self.blocks3):
+            for m in stage:
+                if isinstance(m, EfficientViTBlock) and hasattr(m, 'mixer'):
+                    t = m.forward_tokens(t)
+                elif _is_dw_ffn(m):
+                    t = dw_ffn_tokens(m[0], m[1], t)
+                else:                               # PatchMerging: the framework, on the channels-last view
+                    t = m(t.permute(0, 3, 1, 2)).permute(0, 2, 3, 1)
+        return t.mean((1, 2))
+
     def forward(self, x):
-        x = self.blocks3(self.blocks2(self.blocks1(self.patch_embed(x))))
-        x = F.adaptive_avg_pool2d(x, 1).flatten(1)
+        if self.is_tokens(x):
+            x = self.forward_tokens(x)
+        else:
+            x = self.blocks3(self.blocks2(self.blocks1(self.patch_embed(x))))
+            x = F.adaptive_avg_pool2d(x, 1).flatten(1)
         if not self.distillation:
             return self.head(x)
         x = self.head(x), self.head_dist(x)

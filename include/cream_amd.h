@@ -24,6 +24,10 @@ extern "C" {
 #define CREAM_ERR_BAD_DTYPE   -2  /* dtype enum not supported by this entry point        */
 #define CREAM_ERR_LAUNCH      -3  /* hipLaunchKernel reported an error (see hipGetLastError) */
 #define CREAM_ERR_TOO_LARGE   -4  /* shape exceeds what the kernel family supports       */
+/* the finer codes of the cream_evit_* checks (the older entry points fold them into BAD_ARG) */
+#define CREAM_ERR_CHANNEL_STRIDE -5  /* the channel stride of a (B, H, W, C) view is not 1      */
+#define CREAM_ERR_BAD_STRIDE  -6  /* a batch / row / column stride is negative, not a multiple of 8, or tokens overlap */
+#define CREAM_ERR_BAD_SHAPE   -7  /* a channel count or a map size outside the covered range */
 
 /* ---- element types (the "dtype" argument) ------------------------------------------ */
 #define CREAM_F32   0
@@ -610,6 +614,56 @@ int cream_cga_attn_check(const cream_cga_desc* d);
 
 /* out from x and the folded operands.  One launch. */
 int cream_cga_attn_fwd(const cream_cga_desc* d, void* stream);
+
+/* ---- EfficientViT's depthwise 3 x 3 + FFN pair and proj + residual on the token layout, inference (csrc/evit_ffn.hip) ----
+ * What  ffn(dw(x))  of an EfficientViTBlock (EfficientViT/classification/model/efficientvit.py:263-282: two Residuals, around a
+ * depthwise 3 x 3 Conv2d_BN and around FFN = pw1 -> ReLU -> pw2, :92-101) computes in eval mode, BatchNorm folded, one launch:
+ *     y1  = x + sum_k taps[k] x(y + k / 3 - 1, x + k % 3 - 1) + dwb          zero outside the token's own map
+ *     out = y1 + W2 relu(W1 y1 + b1) + b2
+ * Rounding: the taps, dwb and y1 fp32; the first product reads bf16(y1), accumulates in fp32, then + b1, ReLU, one rounding to
+ * bf16; the second product accumulates in fp32 on top of the fp32 y1; out = bf16(.. + b2).  y1 and the hidden activation never
+ * reach memory.  Ranges: 16 <= C <= 384 in steps of 16, 32 <= Ch <= 768 in steps of 32, B, H, W >= 1.  Every pointer 16-byte
+ * aligned.  x is a strided view with channel stride 1 and batch / row / column strides that are multiples of 8 elements with
+ * xsx >= C: a token tensor, a slice of a larger buffer, a channels-last NCHW tensor.  The checks return, in this order:
+ * CREAM_ERR_BAD_SHAPE (C, Ch, B, H, W), CREAM_ERR_TOO_LARGE (B H W > 2^31 - 65), CREAM_ERR_BAD_ARG (a null or misaligned
+ * pointer), CREAM_ERR_CHANNEL_STRIDE, CREAM_ERR_BAD_STRIDE — before any HIP call.  One workgroup per 64 consecutive tokens (not
+ * persistent), no atomics, no scratch. */
+typedef struct cream_evit_dwffn_desc {
+    const void* x;                  /* bf16, element (b, y, x, c) at b xsb + y xsy + x xsx + c xsc              */
+    int64_t xsb, xsy, xsx, xsc;     /* in elements; xsc must be 1                                              */
+    const float* taps;              /* (9, C): tap k = 3 ky + kx of channel c at k C + c                       */
+    const float* dwb;               /* (C)                                                                     */
+    const void* w1;                 /* bf16 (Ch, KP), KP = C rounded up to 32, zeros past C                    */
+    const float* b1;                /* (Ch)                                                                    */
+    const void* w2;                 /* bf16 (C, Ch)                                                            */
+    const float* b2;                /* (C)                                                                     */
+    void* out;                      /* bf16 (B, H, W, C) contiguous                                            */
+    int32_t B, H, W, C, Ch;
+} cream_evit_dwffn_desc;
+
+/* CREAM_OK when cream_evit_dwffn_fwd would launch for this descriptor, its error code otherwise.  Pure host arithmetic. */
+int cream_evit_dwffn_check(const cream_evit_dwffn_desc* d);
+
+/* out from x and the folded operands.  One launch. */
+int cream_evit_dwffn_fwd(const cream_evit_dwffn_desc* d, void* stream);
+
+/* out = res + W a + b: the 1 x 1 Conv2d_BN `proj` of CascadedGroupAttention (:127-128) on the output of cream_cga_attn_fwd
+ * (which applies the ReLU in front of it) with the mixer's Residual folded in.  out = bf16(fp32(res) + b + fp32 products).
+ * 16 <= Cin, Cout <= 384 in steps of 16; a and res are strided views under the rules of x above; the same codes. */
+typedef struct cream_evit_pw_desc {
+    const void* a;                  /* bf16 (B, H, W, Cin) view                                                */
+    int64_t asb, asy, asx, asc;
+    const void* res;                /* bf16 (B, H, W, Cout) view                                               */
+    int64_t rsb, rsy, rsx, rsc;
+    const void* w;                  /* bf16 (Cout, KP), KP = Cin rounded up to 32, zeros past Cin              */
+    const float* b;                 /* (Cout)                                                                  */
+    void* out;                      /* bf16 (B, H, W, Cout) contiguous                                         */
+    int32_t B, H, W, Cin, Cout;
+} cream_evit_pw_desc;
+
+int cream_evit_pw_residual_check(const cream_evit_pw_desc* d);
+
+int cream_evit_pw_residual_fwd(const cream_evit_pw_desc* d, void* stream);
 
 /* ---- the relation losses of the Mini-Swin distillation step (csrc/distill_loss.hip) -------------------------------
  * cal_relation_loss and cal_hidden_relation_loss of MiniViT/Mini-Swin/main.py:39-57 and :66-77, each with the gradient
