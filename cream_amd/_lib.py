@@ -165,6 +165,9 @@ SIGNATURES = {
     "cream_gemm_nthalf": (_i, [_i]),
     "cream_gemm_nt224": (_i, [_i]),
     "cream_gemm_nt224_launches": (_i64, []),
+    "cream_gemm_ntrow": (_i, [_i]),
+    "cream_gemm_ntrow_launches": (_i64, []),
+    "cream_linear_ntrow": (_i, [_vp, _i64, _vp, _i64, _vp, _i, _i, _i, _i64, _i, _i64, _vp]),
     "cream_linear_nt224": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i64, _i, _i64, _i, _i64, _vp]),
     "cream_gemm_ntopt": (_i, [_i]),
     "cream_gemm_stagger": (_i, [_i]),

@@ -23,6 +23,7 @@
 #include "gemm_mfma.hpp"
 #include "gemm_nt8.hpp"
 #include "gemm_nt224.hpp"
+#include "gemm_ntrow.hpp"
 #include "gemm_tn8.hpp"
 #include "launch_ev.hpp"
 #include "cu_budget.hpp"
@@ -183,9 +184,47 @@ int launch_nt224(const NtParams& p, hipStream_t st)
     return hipGetLastError() == hipSuccess ? CREAM_OK : CREAM_ERR_LAUNCH;
 }
 
+// A full-row 256 x E tile (gemm_ntrow.hpp: 4 x 2 waves of 64 x E / 2 on 32x32x16 MFMAs, two 64-deep stages = 160 / 144 KB of LDS, one
+// persistent workgroup per CU walking 256-row panels) for the input gradients whose output is E = 384 or 320 wide (fc1, qkv, proj at
+// E / 64 heads): one workgroup per row panel ingests 256 + E operand rows per K-step where the two column tiles of the 256 x 192 route
+// ingest 2 x 256 + E, and the product asks for 99 CUs once instead of 198 slots beside the weight-gradient stream.
+// Routing rule (launch_nt, ahead of the 256 x 192 route): plain-store epilogue only, M >= 1024, N == 384 or 320, offsets that fit.
+// Same contraction order per output element as the tiles it replaces: bit-identical results (tests/test_gemm_ntrow_gpu.py).
+// Step, same call, the parent commit's build against this tile on, alternating x4 (profiles/NOTES_nt_fullrow.md): 8.449 / 8.430 / 8.459 /
+// 8.415 -> 8.250 / 8.236 / 8.257 / 8.250 ms (-2.3 %, no overlap).  With the tile on the weight-gradient share stays at 128 CUs
+// (CREAM_WGRAD_CUS 144 / 152: 8.454 / 8.458 and 8.469 / 8.454 ms).
+// CREAM_GEMM_NTROW in the environment / cream_gemm_ntrow(): 0 = off, 1 = on (default).  No workspace layout depends on it.
+EnvSwitch g_ntrow{"CREAM_GEMM_NTROW", 1, norm_bool};
+int ntrow_mode() { return g_ntrow.get(); }
+std::atomic<int64_t> g_ntrow_launches{0};   // cream_gemm_ntrow_launches(): lets a test see which kernel a routed call reached
+
+bool ntrow_fits(const NtParams& p)
+{
+    // 32-bit byte offsets per lane: from the panel origin of A, from p.B for the whole (segmented) B
+    const int64_t amax = (int64_t)NTROW_BM * p.lda, bmax = (int64_t)2 * p.nseg_stride + (int64_t)p.nseg * p.ldb + p.ldb;
+    return p.lda > 0 && p.ldb > 0 && p.nseg_stride >= 0 && amax < ((int64_t)1 << 30) && bmax < ((int64_t)1 << 30) &&
+           (int64_t)p.N * p.ldb < ((int64_t)1 << 30);
+}
+
+template <int BN>
+int launch_ntrow(const NtParams& p, hipStream_t st)
+{
+    auto kern = gemm_ntrow_kernel<BN>;
+    constexpr int lds = ntrow_lds_bytes(BN);
+    if (!cream::raise_dynamic_lds(kern, lds)) return CREAM_ERR_LAUNCH;
+    const int panels = (p.M + NTROW_BM - 1) / NTROW_BM, slots = num_cus();
+    CREAM_LAUNCH(kern, dim3(panels < slots ? panels : slots), dim3(512), lds, st, p);
+    g_ntrow_launches.fetch_add(1, std::memory_order_relaxed);
+    return hipGetLastError() == hipSuccess ? CREAM_OK : CREAM_ERR_LAUNCH;
+}
+
 template <int EPI>
 int launch_nt(const NtParams& p, hipStream_t st)
 {
+    if constexpr (EPI == EPI_STORE) {
+        if (ntrow_mode() > 0 && p.M >= 1024 && (p.N == 384 || p.N == 320) && ntrow_fits(p))
+            return p.N == 384 ? launch_ntrow<384>(p, st) : launch_ntrow<320>(p, st);
+    }
     if constexpr (EPI == EPI_STORE || EPI == EPI_BIAS) {
         if (nt224_mode() > 0 && p.M >= 1024) {
             if (p.N == 448) return launch_nt224<EPI>(p, st);
@@ -287,6 +326,8 @@ int cream_gemm_nt256(int on) { return g_nt256.set(on); }
 int cream_gemm_nthalf(int on) { return g_nthalf.set(on); }
 int cream_gemm_nt224(int on) { return g_nt224.set(on); }
 int64_t cream_gemm_nt224_launches(void) { return g_nt224_launches.load(std::memory_order_relaxed); }
+int cream_gemm_ntrow(int on) { return g_ntrow.set(on); }
+int64_t cream_gemm_ntrow_launches(void) { return g_ntrow_launches.load(std::memory_order_relaxed); }
 int cream_gemm_ntopt(int mode) { return g_ntopt.set(mode); }
 int cream_gemm_stagger(int n) { return g_stagger.set(n); }
 int cream_gemm_nt8(int mode) { return g_nt8.set(mode); }
@@ -329,6 +370,22 @@ int cream_linear_nt224(void* out, const void* x, const void* w, const void* bias
     }
     p.bias = (const uint16_t*)bias;
     return bias ? launch_nt224<EPI_BIAS>(p, (hipStream_t)stream) : launch_nt224<EPI_STORE>(p, (hipStream_t)stream);
+}
+
+int cream_linear_ntrow(void* out, int64_t ldo, const void* x, int64_t ldx, const void* w, int M, int N, int K, int64_t ldw, int kseg,
+                       int64_t kseg_stride, void* stream)
+{
+    const int rc = check_nt(out, x, w, M, N, K, ldw, kseg > 0 && kseg < K ? kseg : K);
+    if (rc) return rc < 0 ? rc : CREAM_OK;
+    if ((N != 384 && N != 320) || ldo < N || ldo % 8 || ldx < K || ldx % 8) return CREAM_ERR_BAD_ARG;
+    NtParams p = plain(out, x, w, M, N, K, ldw);
+    p.lda = ldx; p.ldo = ldo;
+    if (kseg > 0) {
+        if (kseg % 64 || K % kseg || kseg_stride % 8) return CREAM_ERR_BAD_ARG;
+        p.kseg = kseg; p.kseg_stride = kseg_stride;
+    }
+    if (!ntrow_fits(p)) return CREAM_ERR_BAD_ARG;
+    return N == 384 ? launch_ntrow<384>(p, (hipStream_t)stream) : launch_ntrow<320>(p, (hipStream_t)stream);
 }
 
 int cream_linear_gelu_fwd_pad(void* gp, void* g, const void* x, const void* w, const void* bias, int M, int N, int Nvalid,

@@ -912,6 +912,18 @@ int64_t cream_gemm_nt224_launches(void);
  * cream_linear_dgrad_seg (K % kseg == 0, kseg % 64 == 0); 0 = one segment.  M arbitrary, N % 8 == K % 8 == ldw % 8 == 0. */
 int cream_linear_nt224(void* out, const void* x, const void* w, const void* bias, int M, int N, int K, int64_t ldw, int nseg,
                        int64_t nseg_stride, int kseg, int64_t kseg_stride, void* stream);
+/* A full-row 256 x E tile (csrc/gemm_ntrow.hpp, launch_ntrow in csrc/gemm_mfma.hip) for the plain-store products (the input
+ * gradients cream_linear_dgrad / cream_linear_dgrad_seg) whose output is exactly 384 or 320 wide at M >= 1024: one persistent
+ * workgroup per CU walks 256-row panels.  1 = on (default), 0 = off, < 0 queries; returns the previous value; initial:
+ * CREAM_GEMM_NTROW.  Results are bit-identical to the switch-off route.  No workspace layout depends on the switch. */
+int cream_gemm_ntrow(int on);
+/* Launches of that tile by this process so far: a test reads it around a call to see which kernel the call reached. */
+int64_t cream_gemm_ntrow_launches(void);
+/* The same tile whatever the switch says (tests, probes): out(M x N, row stride ldo) = x(M x K, row stride ldx) . W(N x K)^T, plain
+ * store.  N must be 384 or 320; kseg > 0: the contraction in segments as cream_linear_dgrad_seg (K % kseg == 0, kseg % 64 == 0);
+ * 0 = one segment.  M arbitrary, K % 8 == ldw % 8 == ldo % 8 == ldx % 8 == 0. */
+int cream_linear_ntrow(void* out, int64_t ldo, const void* x, int64_t ldx, const void* w, int M, int N, int K, int64_t ldw, int kseg,
+                       int64_t kseg_stride, void* stream);
 int cream_gemm_nt8(int mode);
 /* Round 6: the two-stage NT kernels with their tile epilogue taken off the memory counters (csrc/gemm_mfma.hpp, "OPT"):
  * bit 0 = LDS-DMA as asm, LDS-only epilogue barriers, side inputs (bias, the x gelu' factor rows) requested under the first
